@@ -20,7 +20,11 @@ process of its own, shared by every rank: binds are real REST writes, the pod co
 (rank 0 only, worker 0 of a replica) follows a real chunked watch. `--inproc-api` gives each
 rank an in-process store instead (round 1's extender-isolated setup; `value_inproc_api`).
 `value` = pods bound per second over the K timed steps (whole job, all ranks).
-`value_rtt2ms` repeats the run with a 2 ms round trip on every API answer.
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds every side
+measurement after the timed steps: the `--*-variant` passes (`value_rtt2ms` repeats the run with
+a 2 ms round trip on every API answer; steady churn, a 1000-node cluster, the decisive filter,
+the in-process API, independent schedulers) and the reference algorithm's offline replay.
+`--dump-outputs DIR` writes what the last timed step computed as .npy arrays (dump_outputs).
 The stand-in is C++ by default (kube-scheduler is compiled Go; the Python stand-in's
 interpreter time per pod exceeded the extender's and capped the rate): `--driver python`
 selects the Python one, `--inproc-driver` runs a Python stand-in inside the extender's
@@ -124,6 +128,16 @@ def parse_args():
                          "native watch thread)")
     ap.add_argument("--no-gpu", action="store_true", help="skip GPU discovery (CPU-only rehearsal)")
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement: the --*-variant passes "
+                         "(steady churn, independent schedulers, large cluster, API round trip, decisive "
+                         "filter, in-process API) and the reference algorithm's offline replay "
+                         "(frag_pct_reference_model). Without it a run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: "
+                         "every GPU's free percent and free HBM at the burst's peak (the /status body as "
+                         "arrays, nodes x GPUs) and the ledger's fragmentation figures")
     ap.add_argument("--cpu-profile-out", default="",
                     help="native CPU sampling profile of the headline pass's timed steps (rank 0's "
                          "extender process, every thread, symbolized) as JSON into this file")
@@ -469,7 +483,8 @@ def headline_line(d: Dist, args, res: dict, out: dict, cpus: list[int], api_proc
     }
     if res.get("io_per_pod") is not None:
         full["io_per_pod_rank0"] = res["io_per_pod"]
-    full.update(reference_model_frag(args, topo))
+    if args.full:   # the reference algorithm's offline replay of the timed bursts
+        full.update(reference_model_frag(args, topo))
     if variant is not None:
         tag = f"rtt{args.rtt_variant_ms:g}ms"
         if "error" in variant:
@@ -589,7 +604,7 @@ def main() -> int:
         res = run_pass(d, args, topo, conn, "main", api_proc)
         args._headline = False
         shared_api = not args.inproc_api
-        if args.steady_variant_steps > 0 and not args.steady and shared_api:
+        if args.full and args.steady_variant_steps > 0 and not args.steady and shared_api:
             # steady-state churn (BASELINE config 5 at scale): the cluster is never emptied
             # placement quality is a property of the deployment that exists: ONE kube-scheduler
             # (with N > 1 ranks, its binds spread over every rank's worker)
@@ -601,7 +616,7 @@ def main() -> int:
                 steady_v = (s_args, steady_v[1], summarize(d, s_args, steady_v[1]))
             except Exception as e:
                 steady_v = {"error": f"{type(e).__name__}: {e}"}
-        if d.world > 1 and args.independent_variant_steps > 0 and args.one_scheduler and not args.steady:
+        if args.full and d.world > 1 and args.independent_variant_steps > 0 and args.one_scheduler and not args.steady:
             # N kube-schedulers, one per worker: what the workers sustain when the one
             # scheduler's serial cycle is not the limit (a deployment nobody runs; labelled)
             o_args = argparse.Namespace(**{**vars(args), "one_scheduler": False,
@@ -611,7 +626,7 @@ def main() -> int:
                 one_v = summarize(d, o_args, run_pass(d, o_args, topo, conn, "one", api_proc))
             except Exception as e:
                 one_v = {"error": f"{type(e).__name__}: {e}"}
-        if (args.nodes_variant > 0 and args.nodes_variant_steps > 0 and args.nodes_variant != args.nodes
+        if (args.full and args.nodes_variant > 0 and args.nodes_variant_steps > 0 and args.nodes_variant != args.nodes
                 and not args.steady and shared_api):
             # a large cluster behind kube-scheduler's node sampling: the extender sees only the
             # share of feasible nodes numFeasibleNodesToFind lets through, from a rotating start
@@ -623,7 +638,7 @@ def main() -> int:
                 nodes_v = (n_args, r, summarize(d, n_args, r))
             except Exception as e:
                 nodes_v = {"error": f"{type(e).__name__}: {e}"}
-        if args.rtt_variant_ms > 0:
+        if args.full and args.rtt_variant_ms > 0:
             # the same burst with a modelled API-server round trip on every API call (untimed
             # for `value`; its own clock): what the pods/s above excludes
             v_args = argparse.Namespace(**{**vars(args), "api_rtt_ms": args.rtt_variant_ms,
@@ -632,7 +647,7 @@ def main() -> int:
                 variant = summarize(d, v_args, run_pass(d, v_args, topo, conn, "rtt", api_proc))
             except Exception as e:   # the headline result stands; say what failed
                 variant = {"error": f"{type(e).__name__}: {e}"}
-        if args.decisive_variant_steps > 0 and not args.decisive_filter and not args.steady and not args.compat:
+        if args.full and args.decisive_variant_steps > 0 and not args.decisive_filter and not args.steady and not args.compat:
             x_args = argparse.Namespace(**{**vars(args), "decisive_filter": True,
                                            "steps": args.decisive_variant_steps, "warmup": 1,
                                            "api_rtt_ms": 0.0})
@@ -641,7 +656,7 @@ def main() -> int:
                 dec_v = {"res": r, "out": summarize(d, x_args, r)}
             except Exception as e:
                 dec_v = {"error": f"{type(e).__name__}: {e}"}
-        if args.inproc_variant_steps > 0 and not args.inproc_api:
+        if args.full and args.inproc_variant_steps > 0 and not args.inproc_api:
             # round 1's extender-isolated setup: an in-process store per rank, no HTTP
             # (each rank its own store: a stand-in per rank, each binding on its own worker)
             i_args = argparse.Namespace(**{**vars(args), "inproc_api": True, "api_rtt_ms": 0.0, "one_scheduler": False,
@@ -663,6 +678,8 @@ def main() -> int:
         if api_proc is not None:
             api_proc.close()
     out = summarize(d, args, res)
+    if d.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     if d.rank == 0:
         final_cpus = args._placement["cpus"] if getattr(args, "_placement", None) else cpus
         line, diag = headline_line(d, args, res, out, final_cpus, api_proc, gpu_info, topo,
@@ -674,6 +691,28 @@ def main() -> int:
             Path(args.json_out).write_text(json.dumps({**line, "diagnostics": diag}, indent=1))
     d.close()
     return 0
+
+
+FRAG_OUTPUTS = ("frag_pct", "frag_mib", "stranded_pct", "pct_free_total")
+
+
+def dump_outputs(dirname: str, res: dict) -> None:
+    """`--dump-outputs DIR`: what the last timed step of the headline pass computed, as arrays.
+    The workload is seeded (benchlib.burst), so two builds given the same arguments schedule the
+    same pods and can be compared file by file:
+      gpu_pct_free.npy  float32 [nodes, GPUs]  free gpu-percent of every GPU at the burst's peak
+      gpu_mib_free.npy  float64 [nodes, GPUs]  free HBM (MiB) of every GPU at the burst's peak
+      frag.npy          float64 [4]            the ledger's frag_pct, frag_mib, stranded_pct, pct_free_total
+    (a --nodes 64 run writes a few KB; 100,000 nodes would be 10 MB)."""
+    import numpy as np
+
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    devs = res.get("peak_devices") or []
+    np.save(out / "gpu_pct_free.npy", np.array([[g["pct_free"] for g in n] for n in devs], dtype=np.float32))
+    np.save(out / "gpu_mib_free.npy", np.array([[g["mib_free"] for g in n] for n in devs], dtype=np.float64))
+    last = res["frag"][-1] if res.get("frag") else {}
+    np.save(out / "frag.npy", np.array([last.get(k, float("nan")) for k in FRAG_OUTPUTS], dtype=np.float64))
 
 
 def run_pass(d: Dist, args, topo, conn, tag: str, api_proc=None) -> dict:

@@ -802,6 +802,8 @@ async def run_rank(d: Dist, args, topo, ledger_path: str, conn=None, api_proc: A
     # steps (no per-step copy inside the clock): each step only marks how many there are
     bind_marks: list = []
     spent: list = []   # finished steps' pod objects, freed after the timed steps
+    # bench.py --dump-outputs: rank 0 keeps the headline pass's last timed step's cluster state
+    dump_peak = bool(getattr(args, "dump_outputs", "") and getattr(args, "_headline", False) and d.rank == 0)
 
     def mark_binds() -> None:
         if rt.native is not None:
@@ -857,6 +859,9 @@ async def run_rank(d: Dist, args, topo, ledger_path: str, conn=None, api_proc: A
             await barrier()
         with hc:
             frag = rt.state.frag(min(SIZES))
+            if dump_peak and timed_ids and step == timed_ids[-1]:
+                results["peak_devices"] = [(rt.state.ledger.snapshot(i) or {}).get("devices", [])
+                                           for i in rt.state.node_ids(names)]
             phases.update(create_ms=0.0, schedule_ms=1e3 * summary["span_s"])
             client_s = summary.pop("bind_s_all", [])
             if timed:
@@ -909,6 +914,10 @@ async def run_rank(d: Dist, args, topo, ledger_path: str, conn=None, api_proc: A
         srv_ms.setdefault(step, {})["barrier_peak_ms"] = 1e3 * (tb - ts)
         with hc:
             frag = rt.state.frag(min(SIZES))
+            if dump_peak and timed_ids and step == timed_ids[-1]:
+                # --dump-outputs: every GPU of every node as the ledger holds it at this burst's peak
+                results["peak_devices"] = [(rt.state.ledger.snapshot(i) or {}).get("devices", [])
+                                           for i in rt.state.node_ids(names)]
         uids = burst_uids.pop(step)
         t_frag = time.perf_counter()
         srv_ms[step]["frag_ms"] = 1e3 * (t_frag - tb)

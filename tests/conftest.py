@@ -44,6 +44,18 @@ def tmp_shm(tmp_path):
 
 
 @pytest.fixture
+def sock_dir():
+    """A short directory for unix sockets: a socket's path holds 107 characters, and pytest's
+    tmp_path below a deep TMPDIR is longer than that."""
+    import shutil
+    import tempfile
+
+    d = Path(tempfile.mkdtemp(prefix="ngpu-", dir="/tmp"))
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
 def cpu_exclusive():
     """Multi-process bench jobs (several ranks, each with busy front-door threads, plus the API
     server and the stand-ins) measure timing-sensitive things; under `pytest -n` they take turns

@@ -31,7 +31,7 @@ async def wait_for(pred, timeout=10.0):
     return pred()
 
 
-def test_full_stack_agent_extender_kubelet(tmp_path):
+def test_full_stack_agent_extender_kubelet(tmp_path, sock_dir):
     async def main():
         store = FakeKubeStore()
         runner, port = await serve(store)
@@ -44,7 +44,7 @@ def test_full_stack_agent_extender_kubelet(tmp_path):
                                                                                  "annotations": {}}, "status": {}})
                 root = write_mi355x_sysfs(tmp_path / f"sys{i}", 8, "SPX")
                 topo, host = discover(str(root), use_amdsmi=False)
-                pdir = tmp_path / f"dp{i}"
+                pdir = sock_dir / f"dp{i}"
                 pdir.mkdir()
                 api = KubeClient(KubeConfig(server=url))
                 clients.append(api)
@@ -111,7 +111,7 @@ def test_full_stack_agent_extender_kubelet(tmp_path):
     asyncio.run(main())
 
 
-def test_agent_re_registers_after_kubelet_restart(tmp_path):
+def test_agent_re_registers_after_kubelet_restart(tmp_path, sock_dir):
     """kubelet restarts wipe the device-plugin directory and serve a new kubelet.sock: the
     agent notices, serves its socket again and re-registers, and the new kubelet sees the
     devices through ListAndWatch."""
@@ -125,7 +125,7 @@ def test_agent_re_registers_after_kubelet_restart(tmp_path):
         store.add_node({"apiVersion": "v1", "kind": "Node", "metadata": {"name": n, "labels": {},
                                                                          "annotations": {}}, "status": {}})
         topo, host = discover(str(write_mi355x_sysfs(tmp_path / "sys", 8, "SPX")), use_amdsmi=False)
-        pdir = tmp_path / "dp"
+        pdir = sock_dir / "dp"
         pdir.mkdir()
         kl = FakeKubelet(api, n, str(pdir))
         await kl.start()

@@ -129,7 +129,7 @@ def test_terminal_phase_releases_and_restart_counts_terminating_pods():
     asyncio.run(main())
 
 
-def test_agent_keeps_a_terminating_pods_cus_out_of_new_grants(tmp_path):
+def test_agent_keeps_a_terminating_pods_cus_out_of_new_grants(sock_dir):
     """The node agent's CU grant outlives the deletionTimestamp: a pod admitted next to a
     terminating one gets disjoint CUs; the grant goes back when the pod has stopped."""
     from nanogpu.agent.node import NodeAgent
@@ -141,9 +141,9 @@ def test_agent_keeps_a_terminating_pods_cus_out_of_new_grants(tmp_path):
         topo = synthetic_mi355x(1)
         store.add_node(pu.make_node("n0", 1, topo.to_json()))
         api = InProcKube(store)
-        kl = SimKubelet(api, "n0", str(tmp_path))
+        kl = SimKubelet(api, "n0", str(sock_dir))
         await kl.start()
-        agent = NodeAgent(api, "n0", topo, device_plugin=True, plugin_dir=str(tmp_path), health_period_s=0)
+        agent = NodeAgent(api, "n0", topo, device_plugin=True, plugin_dir=str(sock_dir), health_period_s=0)
         await agent.start()
         try:
             await asyncio.wait_for(kl.ready.wait(), 10)
