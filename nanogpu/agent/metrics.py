@@ -17,6 +17,11 @@ format, joined with what it granted:
     nanogpu_container_gpu_percent{namespace,pod,container,device}
     nanogpu_container_cus{...}                                       CUs in its HSA_CU_MASK
     nanogpu_container_hbm_budget_bytes{...}                          its HBM budget
+  per device, once a deep self-test has run (probe/selftest.py; absent before)
+    nanogpu_selftest_last_run_timestamp_seconds{device}, nanogpu_selftest_seconds{device}
+    nanogpu_selftest_cus_checked / _cus_failed / _cus_uncovered{device}
+    nanogpu_selftest_hbm_bytes_checked / _hbm_errors{device}
+    nanogpu_selftest_runs_total{device,result}                       result = pass | fail
 
 A pod's utilisation is its share of its device's busy time: the container's CUs over the
 device's CUs, times `nanogpu_device_busy_percent` (spatial sharing gives each tenant its own
@@ -43,8 +48,10 @@ def _read_int(p: Path) -> int | None:
         return None
 
 
-def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root: str = "") -> str:
-    """Prometheus text exposition of the node's devices and the plugin's live grants."""
+def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root: str = "",
+           selftest: dict | None = None) -> str:
+    """Prometheus text exposition of the node's devices and the plugin's live grants, and of
+    the deep self-test (`NodeAgent.selftest_stats`) once one has run."""
     devs = topo.devices
     minors = render_minors or [128 + 8 * i for i in range(len(devs))]
     health = plugin.health if plugin is not None else [bool(d.healthy) for d in devs]
@@ -123,6 +130,34 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
         family("nanogpu_plugin_id_mismatches_total", "counter",
                "Allocate calls whose kubelet IDs named another device than the container's placement",
                [("", plugin.id_mismatches)])
+    if selftest and selftest.get("reports"):
+        reps = sorted(selftest["reports"].items())
+
+        def rows(f):
+            return [(_labels(device=i), f(r)) for i, r in reps]
+
+        def sweep(key):
+            return lambda r: (r.get("sweep") or {}).get(key, 0)
+
+        def hbm(key):
+            return lambda r: (r.get("hbm") or {}).get(key, 0)
+
+        family("nanogpu_selftest_last_run_timestamp_seconds", "gauge", "when the device's last deep self-test ended",
+               [(_labels(device=i), selftest["at"][i]) for i, _ in reps])
+        family("nanogpu_selftest_cus_checked", "gauge", "CUs whose MFMA pipes and LDS the last deep self-test checked",
+               rows(sweep("cus_seen")))
+        family("nanogpu_selftest_cus_failed", "gauge", "CUs that failed the last deep self-test",
+               rows(lambda r: len((r.get("sweep") or {}).get("failed", []))))
+        family("nanogpu_selftest_cus_uncovered", "gauge", "CUs the last deep self-test was meant to reach and did not",
+               rows(sweep("cus_uncovered")))
+        family("nanogpu_selftest_hbm_bytes_checked", "gauge", "HBM bytes the last deep self-test pattern-checked",
+               rows(hbm("bytes")))
+        family("nanogpu_selftest_hbm_errors", "gauge", "16-byte HBM elements the last deep self-test read back wrong",
+               rows(hbm("errors")))
+        family("nanogpu_selftest_seconds", "gauge", "duration of the device's last deep self-test",
+               rows(lambda r: r.get("seconds", 0)))
+        family("nanogpu_selftest_runs_total", "counter", "deep self-tests run, by result",
+               [(_labels(device=i, result=res), n) for (i, res), n in sorted(selftest.get("runs", {}).items())])
     return "\n".join(out) + "\n"
 
 
@@ -131,7 +166,8 @@ async def serve_metrics(agent, host: str = "0.0.0.0", port: int = 9410):
     from aiohttp import web
 
     async def metrics(_req):
-        text = render(agent.topo, agent.plugin, agent.render_minors(), agent.sysfs_root)
+        text = render(agent.topo, agent.plugin, agent.render_minors(), agent.sysfs_root,
+                      getattr(agent, "selftest_stats", None))
         return web.Response(text=text, content_type="text/plain", charset="utf-8")
 
     async def healthz(_req):

@@ -16,6 +16,7 @@ import asyncio
 import json
 import logging
 import os
+import time
 
 from .. import types as T
 from ..k8s import podutil as pu
@@ -116,7 +117,8 @@ class NodeAgent:
     def __init__(self, api, node_name: str, topo: NodeTopology, host: dict | None = None,
                  device_plugin: bool = True, plugin_dir: str = "", health_period_s: float = 10.0,
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
-                 reconcile_period_s: float = 5.0):
+                 reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
+                 selftest_period_s: float = 0.0):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -127,6 +129,11 @@ class NodeAgent:
         self.sysfs_root = sysfs_root
         self.kubelet_check_s = kubelet_check_s
         self.selftest_failed: set[int] = set()   # devices whose active self-test failed
+        self.selftest_deep = selftest_deep       # probe.selftest.deep_selftest instead of gpu_selftest
+        self.selftest_hbm_mib = selftest_hbm_mib  # cap of the HBM pattern check (0: free HBM less 2 GiB)
+        self.selftest_period_s = selftest_period_s
+        self.selftest_stats: dict | None = None  # last deep report per device, for /metrics
+        self._no_deep_logged = False
         # kubelet's pod-resources API: which container got which device IDs (plugin.reconcile)
         from .podresources import SOCKET as _PR_SOCKET
 
@@ -272,7 +279,8 @@ class NodeAgent:
     def run_selftest(self, P=None) -> list[int] | None:
         """`gpu_selftest` on every HIP device; returns the failed device indices, or None when
         the probe is missing or its device count does not match the topology (HIP orders
-        devices like the KFD nodes the topology is read from)."""
+        devices like the KFD nodes the topology is read from). In deep mode (`selftest_deep`)
+        a probe that has `cu_sweep` runs `probe.selftest.deep_selftest` per device instead."""
         if P is None:
             from ..native import probe
 
@@ -284,7 +292,70 @@ class NodeAgent:
             log.warning("agent %s: %d HIP devices vs %d topology devices: self-test skipped", self.node, n,
                         len(self.topo.devices))
             return None
+        if self.selftest_deep and self._has_deep(P):
+            return sorted(i for i, r in self.run_deep(P).items() if not r.ok)
         return [i for i in range(n) if not gpu_selftest(P, i)]
+
+    def _has_deep(self, P) -> bool:
+        if hasattr(P, "cu_sweep"):
+            return True
+        if not self._no_deep_logged:
+            self._no_deep_logged = True
+            log.warning("agent %s: this probe has no cu_sweep: the basic self-test runs instead of the deep one",
+                        self.node)
+        return False
+
+    def _is_spx(self, i: int) -> bool:
+        gpu = self.topo.devices[i].gpu
+        g = next((g for g in self.topo.gpus if g.index == gpu), None)
+        return g is None or (g.compute_partition or "SPX").upper() == "SPX"
+
+    def deep_plan(self, i: int) -> tuple[list[int] | None, bool] | None:
+        """What a deep self-test may touch on device `i` right now: (CU-mask bits, or None for
+        every CU; whether the HBM check may run), or None to leave the device alone. A device
+        with no grant gets the whole test. A whole GPU (SPX) that is shared gets a sweep of the
+        units no tenant holds and no HBM check; the probe's masks assume the whole chip, so a
+        partition that holds a grant is left alone, as is a device without a free unit."""
+        if self.plugin is None:
+            return None, True
+        dc = self.plugin.cus[i]
+        whole = any(i in a.devices and (len(a.devices) > 1 or a.percent >= 100 or not a.cus)
+                    for a in self.plugin.grants.values())
+        if not whole and not dc.used:
+            return None, True
+        free = dc.free_units()
+        if whole or not free or not self._is_spx(i):
+            return None
+        return [u * dc.unit + k for u in free for k in range(dc.unit)], False
+
+    def run_deep(self, P, plans: dict | None = None) -> dict:
+        """`deep_selftest` on every device its plan allows (`deep_plan`, taken now unless
+        given); returns {device: DeepReport} and keeps the reports for /metrics."""
+        from ..probe.selftest import deep_selftest, free_hbm_bytes
+
+        if plans is None:
+            plans = {i: self.deep_plan(i) for i in range(len(self.topo.devices))}
+        reports = {}
+        for i, plan in sorted(plans.items()):
+            if plan is None:
+                continue
+            bits, hbm = plan
+            nbytes = 0
+            if hbm:
+                try:
+                    nbytes = free_hbm_bytes(P, i, self.selftest_hbm_mib)
+                except Exception:              # the sweep below reports a device that cannot answer
+                    log.exception("agent %s: memory info of device %d failed", self.node, i)
+            r = reports[i] = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes)
+            if self.selftest_stats is None:
+                self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
+            st = self.selftest_stats
+            st["reports"][i], st["at"][i] = r.to_dict(), time.time()
+            key = (i, "pass" if r.ok else "fail")
+            st["runs"][key] = st["runs"].get(key, 0) + 1
+            if not r.ok:
+                log.warning("agent %s: deep self-test failed on device %d: %s", self.node, i, r.describe_failure())
+        return reports
 
     async def selftest(self, P=None) -> list[int] | None:
         """Runs the self-test off the event loop and applies it: failed devices become
@@ -293,6 +364,10 @@ class NodeAgent:
         if failed is None:
             return None
         self.selftest_failed = set(failed)
+        await self._apply_selftest()
+        return failed
+
+    async def _apply_selftest(self) -> None:
         changed = False
         for i, d in enumerate(self.topo.devices):
             ok = i not in self.selftest_failed and d.healthy
@@ -304,7 +379,43 @@ class NodeAgent:
         if changed:
             log.warning("agent %s: self-test failed on devices %s", self.node, sorted(self.selftest_failed))
             await self.api.patch_node(self.node, node_patch(self.topo))
+
+    def _run_periodic(self, P, plans: dict) -> list[int] | None:
+        if P is None:
+            from ..native import probe
+
+            P = probe(required=False)
+        if P is None or P.device_count() != len(self.topo.devices) or not self._has_deep(P):
+            return None
+        return sorted(i for i, r in self.run_deep(P, plans).items() if not r.ok)
+
+    async def selftest_periodic(self, P=None) -> list[int] | None:
+        """One periodic deep run, off the event loop. A shared whole GPU is re-swept on a stream
+        masked to the units no tenant holds at this moment (`deep_plan`), so no tenant's CUs are
+        touched; HBM is checked only on devices without a grant. A grant that arrives while a
+        sweep is in flight shares its new CUs with the sweep until that one ends: 0.26 ms at
+        4 rounds, 1 ms at 16, measured on MI355X (profiles/gpu_calibration.md). Failures are sticky
+        until the agent restarts: this only ever adds to `selftest_failed`, and a later clean
+        run clears nothing. Returns the devices that failed this run, or None when skipped."""
+        plans = {i: self.deep_plan(i) for i in range(len(self.topo.devices))}
+        failed = await asyncio.get_running_loop().run_in_executor(None, self._run_periodic, P, plans)
+        if failed is None:
+            return None
+        self.selftest_failed |= set(failed)
+        await self._apply_selftest()
         return failed
+
+    async def _selftest_loop(self) -> None:
+        while True:
+            await asyncio.sleep(self.selftest_period_s)
+            try:
+                await self.selftest_periodic()
+            except Exception:
+                log.exception("periodic self-test failed to run")
+
+    def start_selftest_loop(self) -> None:
+        if self.selftest_period_s > 0:
+            self.tasks.append(asyncio.ensure_future(self._selftest_loop()))
 
     async def stop(self) -> None:
         for t in self.tasks:
@@ -330,6 +441,19 @@ def build_parser():
     ap.add_argument("--print", action="store_true", help="print the topology annotation and exit")
     ap.add_argument("--selftest", action="store_true",
                     help="run the HIP self-test (HBM copy + MFMA tile) on every device at start-up")
+
+    class _Deep(argparse.Action):              # --selftest-deep implies --selftest
+        def __call__(self, parser, ns, values, option_string=None):
+            ns.selftest = ns.selftest_deep = True
+
+    ap.add_argument("--selftest-deep", action=_Deep, nargs=0, default=False,
+                    help="the start-up self-test checks every CU (MFMA pipes, LDS) and the free HBM with an "
+                         "address-derived pattern instead of one tile and 16 MiB (implies --selftest)")
+    ap.add_argument("--selftest-hbm-mib", type=int, default=0,
+                    help="cap of the deep self-test's HBM check in MiB (0: all free HBM less 2 GiB); "
+                         "only devices without a grant are checked")
+    ap.add_argument("--selftest-period", type=float, default=0.0,
+                    help="seconds between deep re-tests of the CUs no tenant holds (0: off)")
     ap.add_argument("--metrics-port", type=int, default=9410,
                     help="device / pod / container GPU metrics on :PORT/metrics (0: off)")
     ap.add_argument("--pod-resources-socket", default="/var/lib/kubelet/pod-resources/kubelet.sock",
@@ -360,12 +484,15 @@ def main(argv: list[str] | None = None) -> int:
         api = KubeClient(KubeConfig.auto(a.kubeconfig, a.kube_api))
         agent = NodeAgent(api, a.node_name, topo, host, device_plugin=a.advertise == "device-plugin",
                           plugin_dir=a.plugin_dir, sysfs_root=a.sysfs_root,
-                          pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period)
+                          pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
+                          selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
+                          selftest_period_s=a.selftest_period)
         await agent.start()
         if a.selftest:
             failed = await agent.selftest()
             log.info("agent %s: self-test %s", a.node_name,
                      "skipped" if failed is None else f"failed on {failed}" if failed else "passed")
+        agent.start_selftest_loop()
         metrics = None
         if a.metrics_port:
             from .metrics import serve_metrics

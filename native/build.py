@@ -6,6 +6,7 @@ Outputs (git-ignored, but shipped to the GPU box by gpurun):
   native/bin/nanogpu-topo   standalone topology CLI (node agent without Python)
 
 Usage: python native/build.py [--force] [--no-hip] [--sanitize address|thread|undefined]
+                              [--stress plain|asan|tsan] [--selftest-host plain|asan]
 """
 from __future__ import annotations
 
@@ -135,6 +136,21 @@ def build_stress(kind: str = "plain", force: bool = False) -> Path:
     return _done(out, deps, [kind])
 
 
+def build_selftest_host(kind: str = "plain", force: bool = False) -> Path:
+    """Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h,
+    which the probe's kernels share), optionally under ASan+UBSan. No GPU code involved."""
+    out = NATIVE / "bin" / f"nanogpu-selftest-host-{kind}"
+    src = NATIVE / "tests" / "selftest_host_main.cpp"
+    deps = [src, NATIVE / "include" / "nanogpu" / "selftest_host.h", Path(__file__)]
+    if not force and _fresh(out, deps, [kind]):
+        return out
+    out.parent.mkdir(parents=True, exist_ok=True)
+    opt = ["-O2"] if kind == "plain" else ["-O1", "-g", "-fno-omit-frame-pointer"]
+    _run(["g++", "-std=c++17", "-Wall", "-Wextra", *opt, *SANITIZERS[kind], f"-I{NATIVE / 'include'}",
+          str(src), "-o", str(out)])
+    return _done(out, deps, [kind])
+
+
 def build_probe(force: bool = False) -> Path | None:
     hipcc = shutil.which("hipcc") or str(ROCM / "bin" / "hipcc")
     if not Path(hipcc).exists():
@@ -165,9 +181,14 @@ def main() -> None:
     ap.add_argument("--no-hip", action="store_true")
     ap.add_argument("--sanitize", choices=["address", "thread", "undefined"])
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
+    ap.add_argument("--selftest-host", choices=["plain", "asan"],
+                    help="build the stand-alone check of the deep self-test's host arithmetic")
     a = ap.parse_args()
     if a.stress:
         print(build_stress(a.stress, force=a.force))
+        return
+    if a.selftest_host:
+        print(build_selftest_host(a.selftest_host, force=a.force))
         return
     if a.sanitize:
         print(build_core(force=a.force, sanitize=a.sanitize))

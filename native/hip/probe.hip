@@ -11,6 +11,8 @@
 //                   must scale with the CUs granted);
 //   * hbm_copy    — streaming HBM3E bandwidth (16 B/lane, grid >> 256 WGs);
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
+//   * cu_sweep, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA pipes
+//                   and LDS, and free HBM against an address-derived pattern.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
@@ -21,10 +23,13 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
+
+#include "nanogpu/selftest_host.h"
 
 namespace py = pybind11;
 
@@ -119,6 +124,175 @@ __global__ __launch_bounds__(64) void mfma_tile(const __bf16* __restrict__ A, co
   f32x16 c = {};
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   for (int reg = 0; reg < 16; ++reg) C[((reg & 3) + 8 * (reg >> 2) + 4 * h) * 32 + r] = c[reg];
+}
+
+// ---------------------------------------------------------------------------- deep self-test
+
+namespace st = nanogpu::selftest;
+
+constexpr int kSweepBlock = 256;               // 4 waves: one per SIMD's MFMA pipe
+constexpr uint32_t kLdsDwordsFull = 40960;     // 160 KiB: the whole LDS of a gfx950 CU
+enum : int { kInjectNone = 0, kInjectMfma = 1, kInjectLds = 2 };
+
+// Test hook: the workgroup running on CU (xcc, cu_key) flips one bit of data it owns.
+struct SweepInject {
+  int xcc, cu_key, kind;
+  uint32_t lds_off;
+};
+
+// One visit of one CU: every wave runs the exact MFMA chain and compares its accumulators
+// bit for bit with the host's integer tile (C layout as in mfma_tile); the workgroup then
+// writes mix32(i ^ seed) over `n` LDS dwords, reads it back through other threads than the
+// writers, and repeats with the complement. One record per workgroup (selftest_host.h).
+// No spin, no inter-workgroup traffic; every loop is bounded by `n` or a constant.
+__device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const float* __restrict__ expected,
+                                           uint32_t* __restrict__ out, uint32_t seed, SweepInject inj) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  uint32_t xcc, hwid;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+  const bool mine = inj.kind != kInjectNone && xcc == static_cast<uint32_t>(inj.xcc) &&
+                    st::hw_cu_key(hwid) == static_cast<uint32_t>(inj.cu_key);
+
+  f32x16 c = {};
+#pragma unroll
+  for (int s = 0; s < st::kSweepSteps; ++s) {
+    bf16x8 a, b;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      a[j] = static_cast<__bf16>(static_cast<float>(st::sweep_a(s, r, 8 * h + j)));
+      b[j] = static_cast<__bf16>(static_cast<float>(st::sweep_b(s, 8 * h + j, r)));
+    }
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+  bool mfma_bad = false;
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    uint32_t got = __float_as_uint(c[reg]);
+    if (mine && inj.kind == kInjectMfma && tid == 0 && reg == 0) got ^= 1u;
+    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    mfma_bad |= got != __float_as_uint(expected[row * 32 + r]);
+  }
+
+  volatile uint32_t* v = lds;
+  uint32_t bad = st::kNoBadOffset;
+  for (uint32_t pass = 0; pass < 2; ++pass) {
+    const uint32_t flip = pass ? ~0u : 0u;
+    for (uint32_t i = tid; i < n; i += kSweepBlock) v[i] = st::mix32(i ^ seed) ^ flip;
+    __syncthreads();
+    if (pass == 0 && mine && inj.kind == kInjectLds && tid == 0 && inj.lds_off < n) v[inj.lds_off] ^= 1u;
+    __syncthreads();
+    for (uint32_t j = tid; j < n; j += kSweepBlock) {
+      const uint32_t i = n - 1 - j;
+      if (v[i] != (st::mix32(i ^ seed) ^ flip) && i < bad) bad = i;
+    }
+    __syncthreads();
+  }
+
+  // the array has served; its first dwords carry the workgroup's reduction
+  if (tid == 0) {
+    lds[0] = 0;
+    lds[1] = 0;
+    lds[2] = st::kNoBadOffset;
+  }
+  __syncthreads();
+  if (mfma_bad) atomicOr(&lds[0], 1u << wave);
+  if (bad != st::kNoBadOffset) {
+    atomicOr(&lds[0], st::kFailLds);
+    atomicMin(&lds[2], bad);
+  }
+  if (lane == 0) atomicOr(&lds[1], 1u << st::hw_simd(hwid));
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t* o = out + static_cast<size_t>(blockIdx.x) * st::kSweepRecordWords;
+    o[0] = xcc;
+    o[1] = hwid;
+    o[2] = lds[0];
+    o[3] = lds[1];
+    o[4] = lds[2];
+  }
+}
+
+// Holds all 160 KiB, so at most one sweep workgroup is resident per CU and a grid of
+// rounds x CUs workgroups is spread over every enabled CU by the dispatcher.
+__global__ __launch_bounds__(kSweepBlock) void cu_sweep_full(const float* __restrict__ expected,
+                                                             uint32_t* __restrict__ out, uint32_t seed,
+                                                             SweepInject inj) {
+  __shared__ uint32_t lds[kLdsDwordsFull];
+  sweep_body(lds, kLdsDwordsFull, expected, out, seed, inj);
+}
+
+// For a runtime that does not let one block hold a whole CU's LDS: `n` dwords of dynamic
+// LDS, sized by the host to sharedMemPerBlock.
+__global__ __launch_bounds__(kSweepBlock) void cu_sweep_part(const float* __restrict__ expected,
+                                                             uint32_t* __restrict__ out, uint32_t seed,
+                                                             SweepInject inj, uint32_t n) {
+  extern __shared__ uint32_t lds_dyn[];
+  sweep_body(lds_dyn, n, expected, out, seed, inj);
+}
+
+// HBM pattern test in hbm_copy's shape (256 threads, 4 x 16 B per thread in flight,
+// non-temporal, one pass, scalar tail): hbm_fill only writes, hbm_verify only reads.
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+__device__ __forceinline__ u32x4 pattern4(uint64_t i, uint32_t seed, uint32_t pass) {
+  u32x4 p;
+  p[0] = st::pattern_word(i, 0, seed, pass);
+  p[1] = st::pattern_word(i, 1, seed, pass);
+  p[2] = st::pattern_word(i, 2, seed, pass);
+  p[3] = st::pattern_word(i, 3, seed, pass);
+  return p;
+}
+
+__global__ __launch_bounds__(kCopyBlock) void hbm_fill(u32x4* __restrict__ dst, size_t n, uint32_t seed,
+                                                       uint32_t pass) {
+  const size_t base = static_cast<size_t>(blockIdx.x) * (kCopyBlock * kCopyUnroll) + threadIdx.x;
+  if (base + (kCopyUnroll - 1) * kCopyBlock < n) {
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; ++u)
+      __builtin_nontemporal_store(pattern4(base + u * kCopyBlock, seed, pass), dst + base + u * kCopyBlock);
+  } else {
+    for (int u = 0; u < kCopyUnroll; ++u)
+      if (base + u * kCopyBlock < n) dst[base + u * kCopyBlock] = pattern4(base + u * kCopyBlock, seed, pass);
+  }
+}
+
+struct VerifyOut {
+  unsigned long long errors;                 // mismatching 16-byte elements, all passes
+  st::Mismatch slot[st::kMismatchSlots];     // the first ones to report, claimed through `errors`
+};
+
+__device__ __forceinline__ void verify_one(uint64_t i, u32x4 got, uint32_t seed, uint32_t pass, VerifyOut* o) {
+  const u32x4 exp = pattern4(i, seed, pass);
+  if (exp[0] == got[0] && exp[1] == got[1] && exp[2] == got[2] && exp[3] == got[3]) return;
+  const unsigned long long e = atomicAdd(&o->errors, 1ull);   // 64 bit: cannot wrap or saturate
+  if (e >= static_cast<unsigned long long>(st::kMismatchSlots)) return;
+  uint32_t k = 3, ew = exp[3], gw = got[3];
+  if (exp[2] != got[2]) k = 2, ew = exp[2], gw = got[2];
+  if (exp[1] != got[1]) k = 1, ew = exp[1], gw = got[1];
+  if (exp[0] != got[0]) k = 0, ew = exp[0], gw = got[0];
+  st::Mismatch* m = &o->slot[e];
+  m->element = i;
+  m->expected = ew;
+  m->got = gw;
+  m->word = k;
+  m->pad = 0;
+}
+
+__global__ __launch_bounds__(kCopyBlock) void hbm_verify(const u32x4* __restrict__ src, size_t n, uint32_t seed,
+                                                         uint32_t pass, VerifyOut* __restrict__ o) {
+  const size_t base = static_cast<size_t>(blockIdx.x) * (kCopyBlock * kCopyUnroll) + threadIdx.x;
+  if (base + (kCopyUnroll - 1) * kCopyBlock < n) {
+    u32x4 v[kCopyUnroll];
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; ++u) v[u] = __builtin_nontemporal_load(src + base + u * kCopyBlock);
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; ++u) verify_one(base + u * kCopyBlock, v[u], seed, pass, o);
+  } else {
+    for (int u = 0; u < kCopyUnroll; ++u)
+      if (base + u * kCopyBlock < n) verify_one(base + u * kCopyBlock, src[base + u * kCopyBlock], seed, pass, o);
+  }
 }
 
 // ---------------------------------------------------------------------------- host helpers
@@ -552,6 +726,182 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
   return r;
 }
 
+// ---------------------------------------------------------------------------- deep self-test (host)
+
+struct SweepResult {
+  std::vector<uint32_t> words;   // kSweepRecordWords per workgroup
+  int blocks = 0;
+  size_t lds_bytes = 0;
+  double ms = 0.0;
+};
+
+// rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
+// hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
+SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj) {
+  HIP_OK(hipSetDevice(dev));
+  if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
+  int cus = 0;
+  if (mask.empty())
+    cus = cu_count(dev);
+  else
+    for (uint32_t w : mask) cus += __builtin_popcount(w);
+  if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep: the mask enables no CU");
+  SweepResult res;
+  res.blocks = rounds * cus;
+
+  uint32_t n = kLdsDwordsFull;
+  int fit = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    fit = 0;
+  }
+  const bool full = fit >= 1;
+  if (!full) {
+    hipDeviceProp_t p;
+    HIP_OK(hipGetDeviceProperties(&p, dev));
+    n = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
+    fit = 0;
+    if (n < 4 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n * 4u) != hipSuccess ||
+        fit < 1) {
+      (void)hipGetLastError();
+      throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
+    }
+  }
+  res.lds_bytes = static_cast<size_t>(n) * 4;
+  if (inj.kind == kInjectLds && inj.lds_off >= n) throw std::invalid_argument("cu_sweep: inject offset beyond the LDS array");
+
+  std::vector<int32_t> tile(32 * 32);
+  st::sweep_expected(tile.data());
+  std::vector<float> tile_f(tile.begin(), tile.end());
+  DevBuf<float> expected(tile_f.size());
+  HIP_OK(hipMemcpy(expected.p, tile_f.data(), tile_f.size() * sizeof(float), hipMemcpyHostToDevice));
+  const size_t words = static_cast<size_t>(res.blocks) * st::kSweepRecordWords;
+  DevBuf<uint32_t> out(words);
+  Stream stream(mask);
+  Events ev;
+  auto launch = [&](int blocks, SweepInject j) {
+    if (full)
+      hipLaunchKernelGGL(cu_sweep_full, dim3(blocks), dim3(kSweepBlock), 0, stream.s, expected.p, out.p, seed, j);
+    else
+      hipLaunchKernelGGL(cu_sweep_part, dim3(blocks), dim3(kSweepBlock), n * 4u, stream.s, expected.p, out.p, seed,
+                         j, n);
+    HIP_OK(hipGetLastError());
+  };
+  launch(1, SweepInject{-1, -1, kInjectNone, 0});   // loads the code object outside the timed span
+  HIP_OK(hipMemsetAsync(out.p, 0xff, words * sizeof(uint32_t), stream.s));
+  HIP_OK(hipEventRecord(ev.a, stream.s));
+  launch(res.blocks, inj);
+  HIP_OK(hipEventRecord(ev.b, stream.s));
+  res.ms = ev.ms();
+  HIP_OK(hipStreamSynchronize(stream.s));
+  res.words.resize(words);
+  HIP_OK(hipMemcpy(res.words.data(), out.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int b = 0; b < res.blocks; ++b)
+    if (!st::decode_record(res.words.data(), b).written())
+      throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
+  return res;
+}
+
+struct PatternResult {
+  size_t bytes = 0;
+  unsigned long long errors = 0;
+  std::vector<st::Mismatch> first;
+  double fill_gbs = 0.0, verify_gbs = 0.0;
+};
+
+// Fill `bytes` of fresh device memory with the address-derived pattern and verify it, `passes`
+// times (odd passes: the complement). `corrupt` = (byte offset, xor byte) pairs the host applies
+// between a pass's fill and its verify; `verify_seed` < 0 verifies with `seed`.
+PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes,
+                                const std::vector<std::pair<uint64_t, uint32_t>>& corrupt, int64_t verify_seed) {
+  HIP_OK(hipSetDevice(dev));
+  if (bytes == 0 || bytes % 16 != 0) throw std::invalid_argument("hbm_pattern_check: bytes must be a positive multiple of 16");
+  if (passes < 1 || passes > 16) throw std::invalid_argument("hbm_pattern_check: passes in 1..16");
+  for (const auto& c : corrupt)
+    if (c.first >= bytes || c.second > 0xff) throw std::invalid_argument("hbm_pattern_check: corrupt = (offset < bytes, xor byte)");
+  const size_t n = bytes / 16;
+  if ((n + kCopyBlock * kCopyUnroll - 1) / (kCopyBlock * kCopyUnroll) > 0x7fffffffull)   // gridDim.x
+    throw std::invalid_argument("hbm_pattern_check: too large for one launch");
+  const uint32_t vseed = verify_seed < 0 ? seed : static_cast<uint32_t>(verify_seed);
+
+  struct Buf {   // an allocation that does not fit is the caller's to shrink, not a device fault
+    u32x4* p = nullptr;
+    explicit Buf(size_t b) {
+      const hipError_t e = hipMalloc(&p, b);
+      if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        throw std::bad_alloc();
+      }
+      HIP_OK(e);
+    }
+    ~Buf() {
+      if (p) (void)hipFree(p);
+    }
+  } buf(bytes);
+  DevBuf<VerifyOut> vo(1);
+  Stream stream({});
+  Events ev;
+  HIP_OK(hipMemsetAsync(vo.p, 0, sizeof(VerifyOut), stream.s));
+  // n = 0 touches no memory: loads both kernels outside the timed spans
+  hipLaunchKernelGGL(hbm_fill, dim3(1), dim3(kCopyBlock), 0, stream.s, buf.p, size_t(0), seed, 0u);
+  hipLaunchKernelGGL(hbm_verify, dim3(1), dim3(kCopyBlock), 0, stream.s, buf.p, size_t(0), seed, 0u, vo.p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(stream.s));
+  const dim3 grid(copy_grid(n));
+  double fill_ms = 0.0, verify_ms = 0.0;
+  for (int pass = 0; pass < passes; ++pass) {
+    HIP_OK(hipEventRecord(ev.a, stream.s));
+    hipLaunchKernelGGL(hbm_fill, grid, dim3(kCopyBlock), 0, stream.s, buf.p, n, seed, static_cast<uint32_t>(pass));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ev.b, stream.s));
+    fill_ms += ev.ms();
+    for (const auto& c : corrupt) {
+      unsigned char* at = reinterpret_cast<unsigned char*>(buf.p) + c.first;
+      unsigned char byte = 0;
+      HIP_OK(hipMemcpy(&byte, at, 1, hipMemcpyDeviceToHost));
+      byte ^= static_cast<unsigned char>(c.second);
+      HIP_OK(hipMemcpy(at, &byte, 1, hipMemcpyHostToDevice));
+    }
+    HIP_OK(hipEventRecord(ev.a, stream.s));
+    hipLaunchKernelGGL(hbm_verify, grid, dim3(kCopyBlock), 0, stream.s, buf.p, n, vseed, static_cast<uint32_t>(pass), vo.p);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(ev.b, stream.s));
+    verify_ms += ev.ms();
+  }
+  HIP_OK(hipStreamSynchronize(stream.s));
+  VerifyOut h;
+  HIP_OK(hipMemcpy(&h, vo.p, sizeof(VerifyOut), hipMemcpyDeviceToHost));
+  PatternResult res;
+  res.bytes = bytes;
+  res.errors = h.errors;
+  const size_t k = static_cast<size_t>(std::min<unsigned long long>(h.errors, st::kMismatchSlots));
+  res.first.assign(h.slot, h.slot + k);
+  std::stable_sort(res.first.begin(), res.first.end(),
+                   [](const st::Mismatch& a, const st::Mismatch& b) { return a.element < b.element; });
+  const double moved = static_cast<double>(bytes) * passes;
+  res.fill_gbs = moved / (fill_ms * 1e-3) / 1e9;
+  res.verify_gbs = moved / (verify_ms * 1e-3) / 1e9;
+  return res;
+}
+
+SweepInject parse_inject(const py::object& inject) {
+  SweepInject inj{-1, -1, kInjectNone, 0};
+  if (inject.is_none()) return inj;
+  const py::tuple t = inject.cast<py::tuple>();
+  if (t.size() < 3 || t.size() > 4) throw std::invalid_argument("cu_sweep: inject = (xcc, cu_key, kind[, lds_dword])");
+  inj.xcc = t[0].cast<int>();
+  inj.cu_key = t[1].cast<int>();
+  const std::string kind = t[2].cast<std::string>();
+  if (kind == "mfma")
+    inj.kind = kInjectMfma;
+  else if (kind == "lds")
+    inj.kind = kInjectLds;
+  else
+    throw std::invalid_argument("cu_sweep: inject kind is 'mfma' or 'lds'");
+  if (t.size() == 4) inj.lds_off = t[3].cast<uint32_t>();
+  return inj;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_probe, m) {
@@ -605,4 +955,68 @@ PYBIND11_MODULE(_probe, m) {
       "One-direction xGMI rate src -> dst in GB/s: copy kernel pulling over peer access, and SDMA. "
       "Raises TimeoutError when the transfers do not finish within deadline_s (the work is abandoned).");
   py::register_exception<PeerTimeout>(m, "PeerTimeout", PyExc_TimeoutError);
+  m.def(
+      "cu_sweep",
+      [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const py::object& inject) {
+        const SweepInject inj = parse_inject(inject);
+        SweepResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = cu_sweep(dev, mask, rounds, seed, inj);
+        }
+        py::list recs;
+        for (int b = 0; b < r.blocks; ++b) {
+          const st::SweepRecord rec = st::decode_record(r.words.data(), b);
+          recs.append(py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds,
+                                     rec.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.lds_bad)));
+        }
+        py::dict d;
+        d["records"] = recs;
+        d["lds_bytes"] = r.lds_bytes;
+        d["ms"] = r.ms;
+        return d;
+      },
+      py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
+      py::arg("seed") = 0x5eed5eedu, py::arg("inject") = py::none(),
+      "Deep CU check on a CU-masked stream: rounds x CUs workgroups, each holding a CU's whole LDS, run an "
+      "exact bf16 MFMA chain on all 4 waves and a pattern test of the LDS. Records are (xcc, hw_id, fail bits, "
+      "SIMD ids seen, first bad LDS dword or -1). inject = (xcc, cu_key, 'mfma' | 'lds'[, lds dword]) flips one "
+      "bit of that CU's own data (tests).");
+  m.def(
+      "hbm_pattern_check",
+      [](int dev, size_t bytes, uint32_t seed, int passes, const std::vector<std::pair<uint64_t, uint32_t>>& corrupt,
+         const py::object& verify_seed) {
+        const int64_t vseed = verify_seed.is_none() ? int64_t(-1) : int64_t(verify_seed.cast<uint32_t>());
+        PatternResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed);
+        }
+        py::list first;
+        for (const st::Mismatch& mm : r.first)
+          first.append(py::make_tuple(st::mismatch_byte_offset(mm), mm.expected, mm.got));
+        py::dict d;
+        d["bytes"] = r.bytes;
+        d["errors"] = r.errors;
+        d["first"] = first;
+        d["fill_gbs"] = r.fill_gbs;
+        d["verify_gbs"] = r.verify_gbs;
+        return d;
+      },
+      py::arg("device") = 0, py::arg("bytes") = size_t(256) << 20, py::arg("seed") = 0x5eed5eedu,
+      py::arg("passes") = 2, py::arg("corrupt") = std::vector<std::pair<uint64_t, uint32_t>>{},
+      py::arg("verify_seed") = py::none(),
+      "Fills `bytes` of device memory with an address-derived pattern and verifies it (odd passes: the "
+      "complement). errors counts mismatching 16-byte elements over all passes; first = up to 16 of "
+      "(byte offset of the first differing byte, expected word, got word). corrupt = [(byte offset, xor byte)] "
+      "is applied by the host between fill and verify. Raises MemoryError when the buffer cannot be allocated.");
+  m.def(
+      "mem_info",
+      [](int dev) {
+        size_t free_b = 0, total_b = 0;
+        HIP_OK(hipSetDevice(dev));
+        HIP_OK(hipMemGetInfo(&free_b, &total_b));
+        return py::make_tuple(free_b, total_b);
+      },
+      py::arg("device") = 0, "(free bytes, total bytes) of the device's memory.");
 }

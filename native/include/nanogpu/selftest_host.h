@@ -1,0 +1,99 @@
+// Host/device-shared arithmetic of the deep self-test (native/hip/probe.hip: cu_sweep,
+// hbm_fill, hbm_verify). Plain C++ with no HIP dependency, so the host side can be built
+// and run under sanitizers on its own (native/tests/selftest_host_main.cpp). The Python
+// twin of the pattern is nanogpu/probe/selftest.py.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define NANOGPU_HD __host__ __device__
+#else
+#define NANOGPU_HD
+#endif
+
+namespace nanogpu {
+namespace selftest {
+
+// ---- memory pattern ---------------------------------------------------------------------
+// A fixed 32-bit finaliser (the murmur3 one): every input bit reaches every output bit, so
+// neighbouring addresses hold unrelated words.
+NANOGPU_HD inline uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85ebca6bu;
+  x ^= x >> 13;
+  x *= 0xc2b2ae35u;
+  x ^= x >> 16;
+  return x;
+}
+
+constexpr uint32_t kHiMul = 0x9e3779b1u;
+
+// Word k (0..3) of 16-byte element i. The 64-bit word index w = 4 i + k is split into its
+// low and high 32 bits, so no two words of a buffer below 16 TiB share both: the value is a
+// function of the whole address, and aliased address lines are caught, not only stuck bits.
+// Odd passes hold the complement.
+NANOGPU_HD inline uint32_t pattern_word(uint64_t i, uint32_t k, uint32_t seed, uint32_t pass) {
+  const uint64_t w = i * 4 + k;
+  const uint32_t v = mix32(static_cast<uint32_t>(w) ^ seed) ^ (static_cast<uint32_t>(w >> 32) * kHiMul);
+  return (pass & 1u) ? ~v : v;
+}
+
+// ---- MFMA chain -------------------------------------------------------------------------
+// C = sum over steps s of A_s[32x16] * B_s[16x32], small integers rotated per step:
+// |a| <= 3, |b| <= 2, so |C| <= 8 * 16 * 6 = 768 and every fp32 partial sum is exact.
+constexpr int kSweepSteps = 8;
+
+NANOGPU_HD inline int sweep_a(int s, int row, int k) { return (row * 5 + k * 3 + s * 2) % 7 - 3; }
+NANOGPU_HD inline int sweep_b(int s, int k, int col) { return (k * 3 + col * 2 + s) % 5 - 2; }
+
+// Row-major 32x32 expected tile, in integer arithmetic.
+inline void sweep_expected(int32_t out[32 * 32]) {
+  for (int r = 0; r < 32; ++r)
+    for (int c = 0; c < 32; ++c) {
+      int32_t acc = 0;
+      for (int s = 0; s < kSweepSteps; ++s)
+        for (int k = 0; k < 16; ++k) acc += sweep_a(s, r, k) * sweep_b(s, k, c);
+      out[r * 32 + c] = acc;
+    }
+}
+
+// ---- sweep record -----------------------------------------------------------------------
+constexpr int kSweepRecordWords = 5;     // xcc_id, hw_id of wave 0, fail bits, SIMD ids seen, first bad LDS dword
+constexpr uint32_t kFailLds = 1u << 4;   // bits 0..3: the MFMA check of wave 0..3
+constexpr uint32_t kNoBadOffset = 0xffffffffu;
+constexpr uint32_t kRecordUnwritten = 0xffffffffu;   // the host fills the records with 0xff before the launch
+
+// HW_ID (gfx9 family): wave 3:0, SIMD 5:4, pipe 7:6, CU 11:8, SH 12, SE 15:13.
+NANOGPU_HD inline uint32_t hw_cu_key(uint32_t hw_id) { return (hw_id >> 8) & 0xffu; }
+NANOGPU_HD inline uint32_t hw_simd(uint32_t hw_id) { return (hw_id >> 4) & 3u; }
+
+struct SweepRecord {
+  uint32_t xcc, hw_id, fail, simds, lds_bad;
+  bool written() const { return !(xcc == kRecordUnwritten && hw_id == kRecordUnwritten && fail == kRecordUnwritten); }
+};
+
+inline SweepRecord decode_record(const uint32_t* words, size_t block) {
+  const uint32_t* w = words + block * kSweepRecordWords;
+  return SweepRecord{w[0], w[1], w[2], w[3], w[4]};
+}
+
+// ---- mismatch slot ----------------------------------------------------------------------
+constexpr int kMismatchSlots = 16;
+
+struct Mismatch {
+  uint64_t element;
+  uint32_t expected, got, word, pad;
+};
+
+// Offset of the lowest byte in which the two words differ (little-endian), from the buffer's start.
+inline uint64_t mismatch_byte_offset(const Mismatch& m) {
+  const uint32_t d = m.expected ^ m.got;
+  uint32_t b = 0;
+  while (b < 3 && ((d >> (8 * b)) & 0xffu) == 0) ++b;
+  return m.element * 16 + m.word * 4 + b;
+}
+
+}  // namespace selftest
+}  // namespace nanogpu

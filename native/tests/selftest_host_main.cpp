@@ -1,0 +1,75 @@
+// Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h), with
+// no GPU code involved: build it with `python native/build.py --selftest-host asan` to run it
+// under ASan + UBSan. The pinned pattern values are the ones tests/test_selftest_deep.py pins
+// for the Python twin, so the kernels' header and the twin cannot drift apart unnoticed.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "nanogpu/selftest_host.h"
+
+namespace st = nanogpu::selftest;
+
+static int failures = 0;
+
+#define CHECK(cond)                                                    \
+  do {                                                                 \
+    if (!(cond)) {                                                     \
+      std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+      ++failures;                                                      \
+    }                                                                  \
+  } while (0)
+
+int main() {
+  // pattern
+  CHECK(st::mix32(1) == 0x514e28b7u);
+  CHECK(st::mix32(0xdeadbeefu) == 0x0de5c6a9u);
+  CHECK(st::pattern_word(0, 0, 0, 0) == 0u);
+  CHECK(st::pattern_word(0, 3, 0x1234abcdu, 0) == 0x00d1e6ccu);
+  CHECK(st::pattern_word(4095, 1, 0x1234abcdu, 1) == 0x72a42e3du);
+  CHECK(st::pattern_word(1ull << 30, 2, 7, 0) == 0x523a2a7cu);
+  CHECK(st::pattern_word((1ull << 32) + 5, 0, 0x1234abcdu, 0) == 0x47fe4badu);
+  CHECK(st::pattern_word((1ull << 32) + 5, 0, 0x1234abcdu, 1) == 0xb801b452u);
+  CHECK(st::pattern_word((1ull << 34) + 123456789ull, 3, 0xffffffffu, 2) == 0x71ca6542u);
+  for (uint64_t i : {0ull, 77ull, (1ull << 33) + 1})
+    for (uint32_t k = 0; k < 4; ++k) CHECK(st::pattern_word(i, k, 9, 1) == ~st::pattern_word(i, k, 9, 0));
+  // words 2^32 apart (16 GiB) differ: the high half of the word index is in the value
+  CHECK(st::pattern_word(5, 1, 3, 0) != st::pattern_word(5 + (1ull << 30), 1, 3, 0));
+
+  // expected tile: operand ranges, the exactness bound, and one entry by hand
+  for (int s = 0; s < st::kSweepSteps; ++s)
+    for (int i = 0; i < 32; ++i)
+      for (int k = 0; k < 16; ++k) {
+        CHECK(std::abs(st::sweep_a(s, i, k)) <= 3);
+        CHECK(std::abs(st::sweep_b(s, k, i)) <= 2);
+      }
+  std::vector<int32_t> tile(32 * 32);
+  st::sweep_expected(tile.data());
+  bool varied = false;
+  for (int32_t v : tile) {
+    CHECK(std::abs(v) <= 768);
+    varied |= v != tile[0];
+  }
+  CHECK(varied);
+  int32_t acc = 0;
+  for (int s = 0; s < st::kSweepSteps; ++s)
+    for (int k = 0; k < 16; ++k) acc += ((17 * 5 + k * 3 + s * 2) % 7 - 3) * ((k * 3 + 9 * 2 + s) % 5 - 2);
+  CHECK(tile[17 * 32 + 9] == acc);
+
+  // record decode
+  const uint32_t words[10] = {3, 0x0000a5b0u, 0x12, 0xf, 40959, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu,
+                              0xffffffffu};
+  const st::SweepRecord r0 = st::decode_record(words, 0), r1 = st::decode_record(words, 1);
+  CHECK(r0.written() && !r1.written());
+  CHECK(r0.xcc == 3 && st::hw_cu_key(r0.hw_id) == 0xa5 && st::hw_simd(r0.hw_id) == 3);
+  CHECK((r0.fail & st::kFailLds) && (r0.fail & 0xf) == 2 && r0.lds_bad == 40959);
+
+  // mismatch -> byte offset of the lowest differing byte
+  CHECK(st::mismatch_byte_offset(st::Mismatch{4096, 0x11223344u, 0x11223354u, 0, 0}) == 4096ull * 16);
+  CHECK(st::mismatch_byte_offset(st::Mismatch{2, 0x11223344u, 0x91223344u, 3, 0}) == 2 * 16 + 3 * 4 + 3);
+  CHECK(st::mismatch_byte_offset(st::Mismatch{(1ull << 33), 1, 0x101, 1, 0}) == (1ull << 37) + 4 + 1);
+
+  if (failures) return 1;
+  std::puts("selftest host arithmetic ok");
+  return 0;
+}

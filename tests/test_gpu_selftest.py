@@ -1,0 +1,172 @@
+"""Deep self-test on a real MI355X (`pytest -m gpu`): the probe's cu_sweep over every CU, the
+HBM pattern check, and the agent path on top of them. Corruption is applied by the host or in
+data the kernel owns; nothing here makes the device fault."""
+import json
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+MIB = 1 << 20
+SEED = 0x1234ABCD
+BIG = 64 * MIB + 48          # full blocks plus a 3-element tail
+
+
+def record(key: str, value) -> None:
+    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
+    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
+
+    record_fact(key, value)
+
+
+@pytest.fixture(scope="module")
+def P():
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU visible")
+    from nanogpu.native import probe
+
+    return probe(required=True)
+
+
+@pytest.fixture(scope="module")
+def clean(P):
+    """One unmasked sweep, shared by the tests that start from a clean chip."""
+    from nanogpu.probe.selftest import fold_sweep
+
+    r = P.cu_sweep(0, [], 4, SEED)
+    rep = fold_sweep(r["records"], 256)
+    for rounds in (8, 16):          # a coverage shortfall is not a failure: deep_selftest's own policy
+        if rep["cus_uncovered"] == 0:
+            break
+        r2 = P.cu_sweep(0, [], rounds, SEED)
+        r["records"] = list(r["records"]) + list(r2["records"])
+        rep = fold_sweep(r["records"], 256)
+    return r, rep
+
+
+def test_sweep_reaches_every_cu_and_whole_lds(P, clean):
+    r, rep = clean
+    print("sweep:", {k: rep[k] for k in ("cus_seen", "per_xcd", "simds_seen_min")}, r["lds_bytes"], r["ms"])
+    record("deep_selftest_sweep", {"ms_4_rounds": round(r["ms"], 3), "simds_seen_min": rep["simds_seen_min"],
+                                   "lds_bytes": r["lds_bytes"], "cus_seen": rep["cus_seen"]})
+    assert rep["cus_seen"] == 256
+    assert rep["per_xcd"] == {x: 32 for x in range(8)}
+    assert rep["failed"] == [] and rep["cus_uncovered"] == 0
+    assert r["lds_bytes"] == P.device_props(0)["max_shared_per_cu_bytes"]
+
+
+def test_masked_sweep_sees_the_cus_the_census_sees(P):
+    from nanogpu.agent import cumask
+    from nanogpu.probe.selftest import cu_key, fold_sweep
+
+    bits = cumask.DeviceCUs(256, 8).grant("t", 25)
+    words = cumask.mask_words(bits)
+    census = {(x, cu_key(h)) for x, h in P.cu_census(0, words, 2048, 64)}
+    r = P.cu_sweep(0, words, 8, SEED)
+    swept = {(x, cu_key(h)) for x, h, *_ in r["records"]}
+    rep = fold_sweep(r["records"], census)
+    record("deep_selftest_masked_sweep_ms_25pct_8_rounds", round(r["ms"], 3))
+    assert len(census) == 64
+    assert swept == census, (sorted(census - swept), sorted(swept - census))
+    assert rep["failed"] == [] and rep["uncovered"] == [] and rep["cus_seen"] == 64
+
+
+def _a_cu_on_xcd3(rep_records):
+    from nanogpu.probe.selftest import cu_key
+
+    return sorted({cu_key(h) for x, h, *_ in rep_records if x == 3})[5]
+
+
+def test_injected_mfma_fault_fails_exactly_that_cu(P, clean):
+    from nanogpu.probe.selftest import fold_sweep
+
+    key = _a_cu_on_xcd3(clean[0]["records"])
+    r = P.cu_sweep(0, [], 8, SEED, (3, key, "mfma"))
+    rep = fold_sweep(r["records"], 256)
+    assert rep["failed"] == [{"xcc": 3, "cu_key": key, "kinds": ["mfma"], "lds_bad_off": -1}], rep["failed"]
+
+
+@pytest.mark.parametrize("where", ["last", "first"])
+def test_injected_lds_fault_reports_the_offset(P, clean, where):
+    from nanogpu.probe.selftest import fold_sweep
+
+    key = _a_cu_on_xcd3(clean[0]["records"])
+    last = clean[0]["lds_bytes"] // 4 - 1       # 40959 when the workgroup holds all 160 KiB
+    off = last if where == "last" else 0
+    r = P.cu_sweep(0, [], 8, SEED, (3, key, "lds", off))
+    rep = fold_sweep(r["records"], 256)
+    assert rep["failed"] == [{"xcc": 3, "cu_key": key, "kinds": ["lds"], "lds_bad_off": off}], rep["failed"]
+
+
+# 16 B: the tail path alone; one short of 4096 elements, and 4096; the same around the kernel's own
+# block of 1024 elements; full blocks plus a 3-element tail
+@pytest.mark.parametrize("nbytes", [16, 4096 * 16 - 16, 4096 * 16, 1024 * 16 - 16, 1024 * 16, 1024 * 16 + 16, BIG])
+def test_pattern_check_clean(P, nbytes):
+    r = P.hbm_pattern_check(0, nbytes, SEED, 2)
+    assert r["bytes"] == nbytes and r["errors"] == 0 and r["first"] == [], r
+
+
+def test_pattern_check_finds_host_corruption(P):
+    from nanogpu.probe.selftest import pattern_at
+
+    # byte 0, the last byte, the first byte of element 4096, and the last byte before the
+    # kernel's own block boundary (element 1024): four distinct elements
+    corrupt = [(0, 0x01), (BIG - 1, 0x80), (4096 * 16, 0x10), (1024 * 16 - 1, 0x04)]
+    r = P.hbm_pattern_check(0, BIG, SEED, 1, corrupt)
+    assert r["errors"] == 4, r
+    assert [f[0] for f in r["first"]] == sorted(o for o, _ in corrupt)
+    xor = dict(corrupt)
+    for off, expected, got in r["first"]:
+        assert expected == pattern_at(off, SEED, 0)
+        assert got == expected ^ (xor[off] << (8 * (off % 4)))
+    r2 = P.hbm_pattern_check(0, BIG, SEED, 2, corrupt)       # each pass is corrupted and counted
+    assert r2["errors"] == 8, r2
+    offs = sorted(o for o, _ in corrupt)
+    assert sorted(f[0] for f in r2["first"]) == sorted(offs * 2)
+    for off, expected, got in r2["first"]:
+        assert expected in (pattern_at(off, SEED, 0), pattern_at(off, SEED, 1))
+        assert got == expected ^ (xor[off] << (8 * (off % 4)))
+
+
+def test_pattern_check_wrong_seed_counts_every_element(P):
+    r = P.hbm_pattern_check(0, MIB, SEED, 1, [], SEED + 1)
+    assert r["errors"] == 65536, r["errors"]
+    assert len(r["first"]) == 16
+
+
+def test_pattern_verify_keeps_up_with_the_copy(P):
+    """A copy of N bytes reads N and writes N, so a read-only check of N bytes has no reason
+    to take longer: verify_gbs (bytes read per second) >= half the copy's read+write rate,
+    less the 10 % run-to-run spread of streaming numbers on this box."""
+    copy_gbs = P.hbm_bandwidth(0, 1 << 30, 10)
+    r = P.hbm_pattern_check(0, 1 << 30, SEED, 2)
+    print("copy", copy_gbs, "verify", r["verify_gbs"], "fill", r["fill_gbs"])
+    record("deep_selftest_hbm_1GiB", {"copy_gbs": round(copy_gbs, 1), "verify_gbs": round(r["verify_gbs"], 1),
+                                      "fill_gbs": round(r["fill_gbs"], 1)})
+    assert r["errors"] == 0
+    assert r["verify_gbs"] >= 0.5 * copy_gbs * 0.9, (r["verify_gbs"], copy_gbs)
+
+
+def test_deep_selftest_and_agent_on_the_real_device(P):
+    import asyncio
+
+    from nanogpu.agent.metrics import render
+    from nanogpu.agent.node import NodeAgent
+    from nanogpu.native import core
+    from nanogpu.probe.selftest import deep_selftest
+    from nanogpu.topology.model import from_host_json
+
+    rep = deep_selftest(P, 0, hbm_bytes=256 << 20)
+    record("deep_selftest_256MiB", {"seconds": round(rep.seconds, 4), "launches": rep.sweep["launches"],
+                                    "cus_seen": rep.sweep["cus_seen"]})
+    assert rep.ok, rep.to_dict()
+    assert rep.sweep["cus_seen"] == 256 and rep.hbm["bytes"] == 256 << 20 and rep.hbm["errors"] == 0
+    topo = from_host_json(json.loads(core().discover_topology("", True)))
+    agent = NodeAgent(api=None, node_name="box", topo=topo, device_plugin=False, selftest_deep=True,
+                      selftest_hbm_mib=256)
+    failed = asyncio.run(agent.selftest(P)) if len(topo.devices) == P.device_count() else []
+    assert failed == [], failed
+    if agent.selftest_stats:
+        assert 'nanogpu_selftest_cus_checked{device="0"} 256' in render(topo, selftest=agent.selftest_stats)
