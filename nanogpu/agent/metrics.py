@@ -22,6 +22,9 @@ format, joined with what it granted:
     nanogpu_selftest_cus_checked / _cus_failed / _cus_uncovered{device}
     nanogpu_selftest_hbm_bytes_checked / _hbm_errors{device}
     nanogpu_selftest_runs_total{device,result}                       result = pass | fail
+  per device, when the deep self-test also ran matrix paths (--selftest-paths; absent otherwise)
+    nanogpu_selftest_paths_checked{device}                           paths the last run checked on every CU
+    nanogpu_selftest_path_cus_failed{device,path}                    CUs that failed that path
 
 A pod's utilisation is its share of its device's busy time: the container's CUs over the
 device's CUs, times `nanogpu_device_busy_percent` (spatial sharing gives each tenant its own
@@ -158,6 +161,12 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
                rows(lambda r: r.get("seconds", 0)))
         family("nanogpu_selftest_runs_total", "counter", "deep self-tests run, by result",
                [(_labels(device=i, result=res), n) for (i, res), n in sorted(selftest.get("runs", {}).items())])
+        with_paths = [(i, r["paths"]) for i, r in reps if r.get("paths")]
+        family("nanogpu_selftest_paths_checked", "gauge", "matrix paths the last deep self-test ran on every CU",
+               [(_labels(device=i), len(p["checked"])) for i, p in with_paths])
+        family("nanogpu_selftest_path_cus_failed", "gauge", "CUs that failed the matrix path in the last deep self-test",
+               [(_labels(device=i, path=name), len(p["failed"].get(name, [])))
+                for i, p in with_paths for name in p["checked"]])
     return "\n".join(out) + "\n"
 
 

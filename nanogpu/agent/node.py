@@ -118,7 +118,7 @@ class NodeAgent:
                  device_plugin: bool = True, plugin_dir: str = "", health_period_s: float = 10.0,
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
-                 selftest_period_s: float = 0.0):
+                 selftest_period_s: float = 0.0, selftest_paths=None):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -132,6 +132,13 @@ class NodeAgent:
         self.selftest_deep = selftest_deep       # probe.selftest.deep_selftest instead of gpu_selftest
         self.selftest_hbm_mib = selftest_hbm_mib  # cap of the HBM pattern check (0: free HBM less 2 GiB)
         self.selftest_period_s = selftest_period_s
+        # matrix paths every deep sweep also runs (probe.selftest.parse_paths: "all", "a,b" or names)
+        from ..probe.selftest import parse_paths
+
+        self.selftest_paths: list[str] = parse_paths(selftest_paths)
+        if self.selftest_paths:
+            self.selftest_deep = True            # the paths are part of the deep sweep
+        self._no_paths_logged = False
         self.selftest_stats: dict | None = None  # last deep report per device, for /metrics
         self._no_deep_logged = False
         # kubelet's pod-resources API: which container got which device IDs (plugin.reconcile)
@@ -346,7 +353,11 @@ class NodeAgent:
                     nbytes = free_hbm_bytes(P, i, self.selftest_hbm_mib)
                 except Exception:              # the sweep below reports a device that cannot answer
                     log.exception("agent %s: memory info of device %d failed", self.node, i)
-            r = reports[i] = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes)
+            if self.selftest_paths and not hasattr(P, "cu_sweep_paths") and not self._no_paths_logged:
+                self._no_paths_logged = True
+                log.warning("agent %s: this probe has no cu_sweep_paths: the deep self-test runs without the "
+                            "matrix paths", self.node)
+            r = reports[i] = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths)
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
             st = self.selftest_stats
@@ -449,6 +460,22 @@ def build_parser():
     ap.add_argument("--selftest-deep", action=_Deep, nargs=0, default=False,
                     help="the start-up self-test checks every CU (MFMA pipes, LDS) and the free HBM with an "
                          "address-derived pattern instead of one tile and 16 MiB (implies --selftest)")
+    class _Paths(argparse.Action):             # --selftest-paths implies --selftest-deep
+        def __call__(self, parser, ns, values, option_string=None):
+            from ..probe.selftest import parse_paths
+
+            try:
+                ns.selftest_paths = parse_paths(values)
+            except ValueError as e:
+                parser.error(f"{option_string}: {e}")
+            if not ns.selftest_paths:
+                parser.error(f"{option_string}: name at least one path, or 'all'")
+            ns.selftest = ns.selftest_deep = True
+
+    ap.add_argument("--selftest-paths", action=_Paths, default=[], metavar="all|LIST",
+                    help="the deep self-test also runs an exact MFMA chain of these matrix paths on every CU: "
+                         "'all' or a comma-separated list of f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64 "
+                         "(implies --selftest-deep; start-up and periodic runs alike)")
     ap.add_argument("--selftest-hbm-mib", type=int, default=0,
                     help="cap of the deep self-test's HBM check in MiB (0: all free HBM less 2 GiB); "
                          "only devices without a grant are checked")
@@ -486,7 +513,7 @@ def main(argv: list[str] | None = None) -> int:
                           plugin_dir=a.plugin_dir, sysfs_root=a.sysfs_root,
                           pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
-                          selftest_period_s=a.selftest_period)
+                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths)
         await agent.start()
         if a.selftest:
             failed = await agent.selftest()

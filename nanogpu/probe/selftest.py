@@ -13,10 +13,19 @@ one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe.hip)
   verifies it, then does the same with the complement. `pattern_word` / `pattern_at` are the
   host twin of that pattern, so a report (or a test) can state the expected value anywhere.
 
-What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
-and checks HBM only on devices without a grant), and the contents of L2 / Infinity Cache.
+* `cu_sweep_paths` is `cu_sweep` with, in every visit, an exact chain of 8 instructions of each
+  selected matrix path (`PATHS`: f16, fp8, bf8, i8, block-scaled mxfp8 / mxfp6 / mxfp4, f32,
+  f64) on all 4 waves, every accumulator compared bit for bit with a host tile. The operand
+  data is generated as codes and decoded on the host; the decoders, generators and expected
+  tiles below are the Python twin of native/include/nanogpu/selftest_paths_host.h, which
+  states the exactness argument. `fold_paths` reports per CU which paths failed.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--json]` prints one report.
+What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
+and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache, and of
+the matrix unit the 16x16 shapes, the sparse (smfmac) forms, bf6 operands, mixed A / B formats
+and subnormal, Inf and NaN operands.
+
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--json]` prints one report.
 """
 from __future__ import annotations
 
@@ -106,6 +115,337 @@ def fold_sweep(records, expected_cus) -> dict:
             "simds_seen_min": min((bin(c["simds"]).count("1") for c in seen.values()), default=0)}
 
 
+# ---- matrix paths: the Python twin of native/include/nanogpu/selftest_paths_host.h -------------
+
+PATHS = ("f16", "fp8", "bf8", "i8", "mxfp8", "mxfp6", "mxfp4", "f32", "f64")   # bit order of the records
+PATH_STEPS = 8
+PATH_K = {"f16": 16, "fp8": 16, "bf8": 16, "i8": 32, "mxfp8": 64, "mxfp6": 64, "mxfp4": 64, "f32": 2, "f64": 4}
+PATH_CODE_BITS = {"f16": 16, "fp8": 8, "bf8": 8, "i8": 8, "mxfp8": 8, "mxfp6": 6, "mxfp4": 4, "f32": 32, "f64": 64}
+PATH_FORMAT = {"f16": (5, 10, 15), "fp8": (4, 3, 7), "bf8": (5, 2, 15), "i8": (0, 8, 0), "mxfp8": (4, 3, 7),
+               "mxfp6": (2, 3, 1), "mxfp4": (2, 1, 1), "f32": (8, 23, 127), "f64": (11, 52, 1023)}   # ebits, mbits, bias
+PATH_EXP_WINDOW = {"fp8": (5, 6, 7, 8), "bf8": (14, 15, 16, 17), "mxfp8": (7, 8), "mxfp6": (0, 1, 2, 3),
+                   "mxfp4": (0, 1, 2, 3), "f16": (8, 9, 10, 11, 15, 16), "f32": (120, 121, 122, 123, 127, 128),
+                   "f64": (1016, 1017, 1018, 1019, 1023, 1024)}
+PATH_LIMIT_BITS = {"i8": 31, "f64": 53}     # the others accumulate in fp32: 24
+SCALED_PATHS = ("mxfp8", "mxfp6", "mxfp4")
+SCALE_WINDOW = (127, 128)
+
+
+def parse_paths(spec) -> list[str]:
+    """None / "" / [] -> [], "all" -> every path, "a,b" or a list of names -> those, in bit
+    order. Raises ValueError on an unknown name."""
+    if not spec:
+        return []
+    names = list(PATHS) if spec == "all" else [n.strip() for n in spec.split(",")] if isinstance(spec, str) else list(spec)
+    bad = [n for n in names if n not in PATHS]
+    if bad or not names:
+        raise ValueError(f"unknown matrix path(s) {bad}: choose from {', '.join(PATHS)} or 'all'")
+    return [n for n in PATHS if n in names]
+
+
+def path_dim(path: str) -> int:
+    return 16 if path == "f64" else 32
+
+
+def decode_minifloat(code: int, ebits: int, mbits: int, bias: int) -> tuple[int, int]:
+    """(sig, exp) with value = sig * 2^exp of a finite sign / exponent / mantissa code; exponent
+    field 0 is subnormal. Special exponents are the caller's."""
+    m = code & ((1 << mbits) - 1)
+    e = (code >> mbits) & ((1 << ebits) - 1)
+    sig = ((1 << mbits) + m) if e else m
+    return (-sig if (code >> (ebits + mbits)) & 1 else sig), (e if e else 1) - bias - mbits
+
+
+def _value(sig: int, exp: int, negative_zero: bool) -> float:
+    import math
+
+    return -0.0 if negative_zero and sig == 0 else math.ldexp(sig, exp)
+
+
+def decode_e4m3fn(c: int) -> float:
+    """OCP e4m3fn: no Inf, S.1111.111 is NaN, largest 448."""
+    if c & 0x7F == 0x7F:
+        return float("nan")
+    return _value(*decode_minifloat(c, 4, 3, 7), bool(c & 0x80))
+
+
+def decode_e5m2(c: int) -> float:
+    """OCP e5m2: exponent field 31 is Inf (mantissa 0) or NaN."""
+    if (c >> 2) & 0x1F == 0x1F:
+        return float("nan") if c & 3 else float("-inf") if c & 0x80 else float("inf")
+    return _value(*decode_minifloat(c, 5, 2, 15), bool(c & 0x80))
+
+
+def decode_e2m3(c: int) -> float:
+    return _value(*decode_minifloat(c & 0x3F, 2, 3, 1), bool(c & 0x20))
+
+
+def decode_e2m1(c: int) -> float:
+    return _value(*decode_minifloat(c & 0xF, 2, 1, 1), bool(c & 0x8))
+
+
+def decode_e8m0(c: int) -> float:
+    import math
+
+    return float("nan") if c == 0xFF else math.ldexp(1.0, c - 127)
+
+
+def path_decode(path: str, code: int) -> tuple[int, int]:
+    """(sig, exp) of one operand code of `path`."""
+    if path == "i8":
+        c = code & 0xFF
+        return (c - 256 if c & 0x80 else c), 0
+    return decode_minifloat(code, *PATH_FORMAT[path])
+
+
+def _rotl32(x: int, r: int) -> int:
+    r &= 31
+    return ((x << r) | (x >> (32 - r))) & M32
+
+
+def path_step_hash(path: str, op: int, s: int, idx: int) -> int:
+    """One mix32 per (path, op, idx), varied by step with three operations: the generator runs
+    on every wave of every visit, so it is cheap on purpose."""
+    base = mix32(0x9E3779B9 ^ (PATHS.index(path) << 27) ^ (op << 26) ^ (idx << 8))
+    return ((base ^ (base >> (s + 3))) + s * 0x9E3779B9) & M32
+
+
+def path_hash(path: str, op: int, s: int, idx: int, d: int) -> int:
+    """The hash behind dword d (0..15) of a row / column: one rotation of the step's hash."""
+    return _rotl32(path_step_hash(path, op, s, idx), 7 * d + 3)
+
+
+def wide_code(bits: int, mbits: int, bias: int, op: int, s: int, idx: int, k: int, hv: int) -> int:
+    """f16 / f32 / f64: one FINE value ([2, 3), the mantissa below its top bit hashed) per
+    accumulator, times +-1; everything else COARSE (2^-7..2^-4 x 1.xxx)."""
+    sign = hv & (1 << (bits - 1))
+    coarse = sign | ((bias - 7 + ((hv >> mbits) & 3)) << mbits) | (hv & (7 << (mbits - 3)))
+    if k != 0 or s > 1:
+        return coarse
+    fine = sign | ((bias + 1) << mbits) | (hv & ((1 << (mbits - 1)) - 1))
+    one = sign | (bias << mbits)
+    if s == 0:
+        return (coarse if idx & 1 else fine) if op == 0 else one
+    return (one if idx & 1 else 0) if op == 0 else fine
+
+
+def path_dword(path: str, op: int, s: int, idx: int, d: int) -> int:
+    """Dword d of the packed operand row / column, as the kernel holds it."""
+    if path == "f64":
+        k = d >> 1
+        hv = (path_hash(path, op, s, idx, 2 * k + 1) << 32) | path_hash(path, op, s, idx, 2 * k)
+        return (wide_code(64, 52, 1023, op, s, idx, k, hv) >> (32 * (d & 1))) & M32
+    h = path_hash(path, op, s, idx, d)
+    if path == "fp8":
+        return 0x28282828 + (h & 0x9F9F9F9F)
+    if path in ("bf8", "mxfp8"):
+        return 0x38383838 + (h & 0x8F8F8F8F)
+    if path == "f16":
+        return wide_code(16, 10, 15, op, s, idx, 2 * d, h & 0xFFFF) | (wide_code(16, 10, 15, op, s, idx, 2 * d + 1, h >> 16) << 16)
+    if path == "f32":
+        return wide_code(32, 23, 127, op, s, idx, d, h)
+    return h
+
+
+def path_codes(path: str, op: int, s: int, idx: int) -> list[int]:
+    """The K codes of row (op 0) or column (op 1) `idx` at step s: code k is bits
+    [k * code_bits, (k + 1) * code_bits) of the little-endian string of path_dword's."""
+    cb, K = PATH_CODE_BITS[path], PATH_K[path]
+    row = 0
+    for d in range(K * cb // 32):
+        row |= path_dword(path, op, s, idx, d) << (32 * d)
+    return [(row >> (k * cb)) & ((1 << cb) - 1) for k in range(K)]
+
+
+def path_opsel(op: int, s: int) -> int:
+    return (s & 3) if op == 0 else ((s >> 1) & 3)
+
+
+def path_scale(path: str, op: int, s: int, idx: int, block: int) -> int:
+    dword = 0x7F7F7F7F + (_rotl32(path_step_hash(path, op, s, idx), 19 + 6 * block) & 0x01010101)
+    return (dword >> (8 * path_opsel(op, s))) & 0xFF
+
+
+def _operand_ints(path: str, codes, scales=None):
+    """Rows of codes -> (rows of Python ints, exponent of their common unit). `scales[i][k // 32]`
+    (E8M0) multiplies row i."""
+    dec = [[path_decode(path, c) for c in row] for row in codes]
+    if scales is not None:
+        dec = [[(sg, e + scales[i][k // 32] - 127) for k, (sg, e) in enumerate(row)] for i, row in enumerate(dec)]
+    emin = min((e for row in dec for sg, e in row if sg), default=0)
+    return [[sg << (e - emin) if sg else 0 for sg, e in row] for row in dec], emin
+
+
+def exact_product(path: str, a_codes, b_codes, scale_a=None, scale_b=None, acc=None):
+    """The exact product of one instruction on codes, in Python integers: a_codes[row][k],
+    b_codes[k][col], scale_a[row][k block], scale_b[k block][col]. Returns (units, abs_units,
+    unit_exp): dim x dim lists with C = units * 2^unit_exp, and the sums of |term|."""
+    dim, K = path_dim(path), PATH_K[path]
+    bt = [[b_codes[k][c] for k in range(K)] for c in range(dim)]
+    sbt = None if scale_b is None else [[scale_b[blk][c] for blk in range(2)] for c in range(dim)]
+    a, ea = _operand_ints(path, a_codes, scale_a)
+    b, eb = _operand_ints(path, bt, sbt)
+    units = [[sum(x * y for x, y in zip(a[r], b[c])) for c in range(dim)] for r in range(dim)]
+    abs_units = [[sum(abs(x * y) for x, y in zip(a[r], b[c])) for c in range(dim)] for r in range(dim)]
+    return units, abs_units, ea + eb
+
+
+def _trailing_zeros(x: int) -> int:
+    return (x & -x).bit_length() - 1
+
+
+def path_expected(path: str) -> dict:
+    """The expected tile of `path`'s chain of PATH_STEPS instructions on the generated data:
+    {"dim", "units" (row-major ints), "unit_exp", "sum_abs_max", "limit_bits", "exact"}: every
+    term is a multiple of 2^unit_exp (the smallest product exponent), and the chain is exact
+    whatever the hardware's order while sum_abs_max < 2^limit_bits."""
+    dim = path_dim(path)
+    total = [[0] * dim for _ in range(dim)]
+    total_abs = [[0] * dim for _ in range(dim)]
+    steps = []
+    for s in range(PATH_STEPS):
+        a = [path_codes(path, 0, s, r) for r in range(dim)]
+        bt = [path_codes(path, 1, s, c) for c in range(dim)]
+        b = [[bt[c][k] for c in range(dim)] for k in range(PATH_K[path])]
+        sa = sb = None
+        if path in SCALED_PATHS:
+            sa = [[path_scale(path, 0, s, r, blk) for blk in range(2)] for r in range(dim)]
+            sb = [[path_scale(path, 1, s, c, blk) for c in range(dim)] for blk in range(2)]
+        steps.append(exact_product(path, a, b, sa, sb))
+    base = min(e for _, _, e in steps)
+    for units, abs_units, e in steps:
+        for r in range(dim):
+            for c in range(dim):
+                total[r][c] += units[r][c] << (e - base)
+                total_abs[r][c] += abs_units[r][c] << (e - base)
+    # every term is a multiple of 2^tz: the unit is the lowest set bit of the sums of |term|
+    tz = min(_trailing_zeros(v) for row in total_abs for v in row if v)
+    flat = [v >> tz for row in total for v in row]
+    sum_abs_max = max(v >> tz for row in total_abs for v in row)
+    limit = PATH_LIMIT_BITS.get(path, 24)
+    return {"dim": dim, "units": flat, "unit_exp": base + tz, "sum_abs_max": sum_abs_max, "limit_bits": limit,
+            "exact": sum_abs_max < (1 << limit)}
+
+
+def tile_values(path: str, units, unit_exp: int) -> list:
+    """units * 2^unit_exp as the accumulator holds it: ints for i8, floats elsewhere (exact)."""
+    import math
+
+    if path == "i8":
+        return [u << unit_exp if unit_exp >= 0 else u >> -unit_exp for u in units]
+    return [math.ldexp(u, unit_exp) for u in units]
+
+
+def tile_words(path: str, values) -> list[int]:
+    """The 32-bit words the kernel compares: fp32 bit patterns, i32, or (low, high) of each f64."""
+    import struct
+
+    if path == "i8":
+        return [v & M32 for v in values]
+    if path == "f64":
+        out = []
+        for v in values:
+            bits = struct.unpack("<Q", struct.pack("<d", v))[0]
+            out += [bits & M32, bits >> 32]
+        return out
+    return [struct.unpack("<I", struct.pack("<f", v))[0] for v in values]
+
+
+def tile_checksum(words) -> int:
+    """FNV-1a over the words' bytes, low byte first."""
+    h = 0x811C9DC5
+    for w in words:
+        for b in range(4):
+            h = ((h ^ ((w >> (8 * b)) & 0xFF)) * 0x01000193) & M32
+    return h
+
+
+def path_coverage(path: str) -> list[str]:
+    """The coverage conditions `path`'s data does not meet (empty: all hold): "bits" (sign, every
+    mantissa bit and every exponent bit the window varies take both values, in A and in B),
+    "window", "asymmetry", "scales" (differ between rows, k blocks, A and B), "opsel"."""
+    dim, K = path_dim(path), PATH_K[path]
+    ebits, mbits, _bias = PATH_FORMAT[path]
+    unmet = set()
+    need = 0xFF
+    if ebits:
+        win = PATH_EXP_WINDOW[path]
+        e_or = e_and = win[0]
+        for e in win:
+            e_or, e_and = e_or | e, e_and & e
+        need = (1 << (ebits + mbits)) | ((e_or & ~e_and) << mbits) | ((1 << mbits) - 1)
+    codes = [[[path_codes(path, op, s, i) for i in range(dim)] for s in range(PATH_STEPS)] for op in range(2)]
+    full = (1 << PATH_CODE_BITS[path]) - 1
+    for op in range(2):
+        ones = zeros = 0
+        for s in range(PATH_STEPS):
+            for i in range(dim):
+                for c in codes[op][s][i]:
+                    ones |= c
+                    zeros |= ~c & full
+                    if ebits and not (path in ("f16", "f32", "f64") and c == 0):
+                        if (c >> mbits) & ((1 << ebits) - 1) not in PATH_EXP_WINDOW[path]:
+                            unmet.add("window")
+        if ones & zeros & need != need:
+            unmet.add("bits")
+    n = min(dim, K)
+    a_sym = all(codes[0][s][i][k] == codes[0][s][k][i] for s in range(PATH_STEPS) for i in range(n) for k in range(n))
+    b_sym = all(codes[1][s][i][k] == codes[1][s][k][i] for s in range(PATH_STEPS) for i in range(n) for k in range(n))
+    ab_t = all(codes[0][s][i] == codes[1][s][i] for s in range(PATH_STEPS) for i in range(dim))
+    if a_sym or b_sym or ab_t:
+        unmet.add("asymmetry")
+    if path in SCALED_PATHS:
+        sc = {(op, s, i, blk): path_scale(path, op, s, i, blk)
+              for op in range(2) for s in range(PATH_STEPS) for i in range(dim) for blk in range(2)}
+        if any(v not in SCALE_WINDOW for v in sc.values()):
+            unmet.add("scales")
+        rows = any(v != sc[(op, s, 0, blk)] for (op, s, i, blk), v in sc.items())
+        blocks = any(v != sc[(op, s, i, 0)] for (op, s, i, blk), v in sc.items())
+        ab = any(v != sc[(0, s, i, blk)] for (op, s, i, blk), v in sc.items())
+        if not (rows and blocks and ab):
+            unmet.add("scales")
+        if not any(path_opsel(op, s) for op in range(2) for s in range(PATH_STEPS)):
+            unmet.add("opsel")
+    return sorted(unmet)
+
+
+def fold_paths(records, paths, expected_cus) -> dict:
+    """Folds `cu_sweep_paths` records `(xcc, hw_id, fail, simds, lds_bad, path_fail_bits,
+    path_waves)` by CU; `paths` names the bits of `path_fail_bits` in order. A CU failed a path
+    when any of its visits did (a clean revisit clears nothing). `failed` maps each failed path
+    to its `[xcc, cu_key]` list, `cus` lists per failed CU its paths and the waves (bit w: wave
+    w) that saw one fail; `uncovered` / `cus_uncovered` as in `fold_sweep`: not a failure."""
+    paths = list(paths)
+    seen: dict[tuple[int, int], list[int]] = {}
+    for xcc, hw_id, _fail, _simds, _bad, pfail, pwaves in records:
+        c = seen.setdefault((xcc, cu_key(hw_id)), [0, 0])
+        c[0] |= pfail
+        c[1] |= pwaves
+    if isinstance(expected_cus, int):
+        n_expected, uncovered = expected_cus, []
+        n_uncovered = max(0, n_expected - len(seen))
+    else:
+        expected = {tuple(k) for k in expected_cus}
+        n_expected = len(expected)
+        uncovered = sorted(expected - set(seen))
+        n_uncovered = len(uncovered)
+
+    def names(bits: int) -> list[str]:
+        out = [paths[i] for i in range(len(paths)) if bits >> i & 1]
+        return out + (["record"] if bits >> len(paths) else [])
+
+    failed: dict[str, list[list[int]]] = {}
+    cus = []
+    for k, (bits, waves) in sorted(seen.items()):
+        if not bits:
+            continue
+        cus.append({"xcc": k[0], "cu_key": k[1], "paths": names(bits), "waves": waves})
+        for n in names(bits):
+            failed.setdefault(n, []).append([k[0], k[1]])
+    return {"cus_seen": len(seen), "cus_expected": n_expected, "failed": failed, "cus": cus,
+            "uncovered": [list(k) for k in uncovered], "cus_uncovered": n_uncovered}
+
+
 @dataclass
 class DeepReport:
     device: int
@@ -117,6 +457,7 @@ class DeepReport:
     masked: bool = False             # swept only the CUs in `cu_mask_bits`
     seed: int = 0
     notes: list[str] = field(default_factory=list)
+    paths: dict | None = None        # {"checked": [names], "failed": {name: [[xcc, cu_key], ...]}}; None: not run
 
     def to_dict(self) -> dict:
         return asdict(self)
@@ -128,6 +469,8 @@ class DeepReport:
         parts = [f"CU (xcc {f['xcc']}, key {f['cu_key']:#x}) {'+'.join(f['kinds'])}"
                  + (f" at LDS dword {f['lds_bad_off']}" if f["lds_bad_off"] >= 0 else "")
                  for f in (self.sweep or {}).get("failed", [])]
+        for name, where in sorted(((self.paths or {}).get("failed") or {}).items()):
+            parts.append(f"matrix path {name} on " + ", ".join(f"CU (xcc {x}, key {k:#x})" for x, k in where))
         if self.hbm and self.hbm.get("errors"):
             first = self.hbm.get("first") or []
             at = f", first at byte {first[0][0]} (expected {first[0][1]:#010x}, got {first[0][2]:#010x})" if first else ""
@@ -146,16 +489,23 @@ def free_hbm_bytes(P, device: int, cap_mib: int = 0) -> int:
 
 
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
-                  seed: int | None = None, rounds: int = 4) -> DeepReport:
+                  seed: int | None = None, rounds: int = 4, paths=None) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
     the sweep to those CU-mask bits (the agent passes the units no tenant holds; None: the
-    whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory. `ok` is
-    false if and only if a CU failed a check, HBM errors were counted, or HIP raised."""
+    whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory. `paths`
+    (`parse_paths`: None, "all", "a,b" or a list of names) makes the sweep launches
+    `cu_sweep_paths` with those matrix paths instead of `cu_sweep`: still one visit per CU.
+    `ok` is false if and only if a CU failed a check or a path, HBM errors were counted, or
+    HIP raised."""
     from ..agent import cumask
 
     if seed is None:
         seed = int(time.time() * 1000) & M32   # another pattern every run
     rep = DeepReport(device=device, masked=cu_mask_bits is not None, seed=seed)
+    names = parse_paths(paths)
+    if names and not hasattr(P, "cu_sweep_paths"):
+        rep.notes.append("this probe has no cu_sweep_paths: the plain sweep ran and no matrix path was checked")
+        names = []
     t0 = time.perf_counter()
     try:
         cus = int(P.device_props(device)["cus"])
@@ -163,15 +513,17 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         expected = len(set(cu_mask_bits)) if cu_mask_bits is not None else cus
         records, launches, r, last = [], 0, rounds, {}
         while True:
-            last = P.cu_sweep(device, mask, r, seed)
+            last = P.cu_sweep_paths(device, mask, r, seed, names) if names else P.cu_sweep(device, mask, r, seed)
             launches += 1
             records.extend(last["records"])
-            sweep = fold_sweep(records, expected)
+            sweep = fold_sweep([rec[:5] for rec in records], expected)
             if sweep["cus_uncovered"] == 0 or launches >= MAX_LAUNCHES:
                 break
             r *= 2
         sweep.update(lds_bytes=int(last["lds_bytes"]), launches=launches, ms=float(last["ms"]))
         rep.sweep = sweep
+        if names:
+            rep.paths = {"checked": names, "failed": fold_paths(records, last["paths"], expected)["failed"]}
         if sweep["cus_uncovered"]:
             rep.notes.append(f"{sweep['cus_uncovered']} CUs not reached in {launches} launches")
         if hbm_bytes > 0:
@@ -185,7 +537,8 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
                 except MemoryError:
                     rep.notes.append(f"{want} bytes of HBM could not be allocated")
                     want = (want // 2) & ~15
-        rep.ok = not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
+        rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
+                  and not (rep.paths and rep.paths["failed"]))
     except Exception as e:                     # a HIP error is a failed device
         log.exception("deep self-test of device %d raised", device)
         rep.ok, rep.error = False, f"{type(e).__name__}: {e}"
@@ -204,11 +557,17 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--hbm-mib", type=int, default=1024,
                     help="HBM to pattern-check in MiB (default 1024; 0: all free memory less 2 GiB)")
+    ap.add_argument("--paths", default="", metavar="all|LIST",
+                    help="matrix paths every CU also runs: 'all' or a comma-separated list of " + ", ".join(PATHS))
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args(argv)
+    try:
+        names = parse_paths(a.paths)
+    except ValueError as e:
+        ap.error(str(e))
     P = probe(required=True)
     nbytes = free_hbm_bytes(P, a.device, a.hbm_mib)
-    rep = deep_selftest(P, a.device, hbm_bytes=nbytes)
+    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names)
     if a.json:
         print(json.dumps(rep.to_dict()))
     else:
@@ -218,6 +577,10 @@ def main(argv: list[str] | None = None) -> int:
             print(f"  CUs checked {s['cus_seen']}/{s['cus_expected']} (per XCD {s['per_xcd']}), "
                   f"{len(s['failed'])} failed, {s['cus_uncovered']} not reached, LDS {s['lds_bytes']} B per CU, "
                   f"sweep {s['ms']:.3f} ms in {s['launches']} launch(es)")
+        if rep.paths:
+            bad = rep.paths["failed"]
+            print(f"  matrix paths {', '.join(rep.paths['checked'])}: "
+                  + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
                   f"verify {h['verify_gbs']:.0f} GB/s")

@@ -6,7 +6,7 @@ Outputs (git-ignored, but shipped to the GPU box by gpurun):
   native/bin/nanogpu-topo   standalone topology CLI (node agent without Python)
 
 Usage: python native/build.py [--force] [--no-hip] [--sanitize address|thread|undefined]
-                              [--stress plain|asan|tsan] [--selftest-host plain|asan]
+                              [--stress plain|asan|tsan] [--selftest-host plain|asan|paths-plain|paths-asan]
 """
 from __future__ import annotations
 
@@ -136,12 +136,21 @@ def build_stress(kind: str = "plain", force: bool = False) -> Path:
     return _done(out, deps, [kind])
 
 
-def build_selftest_host(kind: str = "plain", force: bool = False) -> Path:
-    """Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h,
-    which the probe's kernels share), optionally under ASan+UBSan. No GPU code involved."""
-    out = NATIVE / "bin" / f"nanogpu-selftest-host-{kind}"
-    src = NATIVE / "tests" / "selftest_host_main.cpp"
-    deps = [src, NATIVE / "include" / "nanogpu" / "selftest_host.h", Path(__file__)]
+SELFTEST_HOST_TARGETS = {   # target -> (program's stem, its main, the headers it checks)
+    "host": ("nanogpu-selftest-host", "selftest_host_main.cpp", ["selftest_host.h"]),
+    "paths": ("nanogpu-selftest-paths-host", "selftest_paths_host_main.cpp",
+              ["selftest_host.h", "selftest_paths_host.h"]),
+}
+
+
+def build_selftest_host(kind: str = "plain", force: bool = False, target: str = "host") -> Path:
+    """Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h, or
+    with target "paths" nanogpu/selftest_paths_host.h, which the probe's kernels share),
+    optionally under ASan+UBSan. No GPU code involved."""
+    stem, main_cpp, headers = SELFTEST_HOST_TARGETS[target]
+    out = NATIVE / "bin" / f"{stem}-{kind}"
+    src = NATIVE / "tests" / main_cpp
+    deps = [src, *[NATIVE / "include" / "nanogpu" / h for h in headers], Path(__file__)]
     if not force and _fresh(out, deps, [kind]):
         return out
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -181,14 +190,16 @@ def main() -> None:
     ap.add_argument("--no-hip", action="store_true")
     ap.add_argument("--sanitize", choices=["address", "thread", "undefined"])
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
-    ap.add_argument("--selftest-host", choices=["plain", "asan"],
-                    help="build the stand-alone check of the deep self-test's host arithmetic")
+    ap.add_argument("--selftest-host", choices=["plain", "asan", "paths-plain", "paths-asan"],
+                    help="build the stand-alone check of the deep self-test's host arithmetic "
+                         "(paths-*: the matrix paths' header)")
     a = ap.parse_args()
     if a.stress:
         print(build_stress(a.stress, force=a.force))
         return
     if a.selftest_host:
-        print(build_selftest_host(a.selftest_host, force=a.force))
+        target, _, kind = a.selftest_host.rpartition("-")
+        print(build_selftest_host(kind, force=a.force, target=target or "host"))
         return
     if a.sanitize:
         print(build_core(force=a.force, sanitize=a.sanitize))

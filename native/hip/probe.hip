@@ -13,6 +13,8 @@
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
 //   * cu_sweep, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA pipes
 //                   and LDS, and free HBM against an address-derived pattern.
+//   * matrix_tile, cu_sweep_paths — the same sweep over the rest of the matrix unit: f16,
+//                   fp8 / bf8, i8, block-scaled fp8 / fp6 / fp4, f32 and f64 MFMA.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "nanogpu/selftest_host.h"
+#include "nanogpu/selftest_paths_host.h"
 
 namespace py = pybind11;
 
@@ -132,21 +135,206 @@ namespace st = nanogpu::selftest;
 
 constexpr int kSweepBlock = 256;               // 4 waves: one per SIMD's MFMA pipe
 constexpr uint32_t kLdsDwordsFull = 40960;     // 160 KiB: the whole LDS of a gfx950 CU
-enum : int { kInjectNone = 0, kInjectMfma = 1, kInjectLds = 2 };
+enum : int { kInjectNone = 0, kInjectMfma = 1, kInjectLds = 2, kInjectPath = 3 };
 
-// Test hook: the workgroup running on CU (xcc, cu_key) flips one bit of data it owns.
+// Test hook: the workgroup running on CU (xcc, cu_key) flips one bit of data it owns
+// (kInjectPath: of path `lds_off`'s accumulator, in cu_sweep_paths only).
 struct SweepInject {
   int xcc, cu_key, kind;
   uint32_t lds_off;
 };
+
+// ---- matrix paths (selftest_paths_host.h) ----
+namespace sp = nanogpu::selftest::paths;
+
+using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x8 = __attribute__((ext_vector_type(8))) int;
+using i32x16 = __attribute__((ext_vector_type(16))) int;
+using f64x4 = __attribute__((ext_vector_type(4))) double;
+
+template <int P> struct AccOf { using type = f32x16; };
+template <> struct AccOf<sp::kI8> { using type = i32x16; };
+template <> struct AccOf<sp::kF64> { using type = f64x4; };
+
+// Operand lane maps, confirmed on MI355X with matrix_tile on asymmetric random codes and
+// scales (tests/test_gpu_selftest_paths.py). Lane l of a 32x32 path holds row (A) or column
+// (B) l & 31; its operand dwords are dwords of the row's little-endian code string, code j of
+// a dword string in bits [j * code_bits, (j + 1) * code_bits).
+//   f16 / fp8 / bf8 32x32x16: k = 8 (l >> 5) + j, j = 0..7;  i8 32x32x32: k = 16 (l >> 5) + j;
+//   f32 32x32x2: k = l >> 5;  f64 16x16x4: lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15].
+//   Scaled 32x32x64, e2m3 and e2m1: k = 32 (l >> 5) + j, j = 0..31, in 6 resp. 4 of the 8
+//   operand dwords (the rest 0): the lane holds one whole 32-element scale block.
+//   Scaled 32x32x64, e4m3: NOT consecutive. Dwords 0..3 hold k = 16 (l >> 5) + j and dwords
+//   4..7 hold k = 32 + 16 (l >> 5) + j, j = 0..15: a lane holds half of each scale block.
+//   Scales, every format: the lane with l >> 5 == b supplies row / column (l & 31)'s E8M0
+//   scale of k block b (k = 32 b .. 32 b + 31), in byte `opsel` (0..3) of its scale register.
+// C / D: 32x32 row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5), col = l & 31, whatever the
+// format; f64: row = (l >> 4) + 4 reg, col = l & 15.
+template <int P> struct LaneMap {
+  static constexpr int kGroupShift = P == sp::kF64 ? 4 : 5;
+  static constexpr int kDwords = sp::path_row_dwords(P) >> (6 - kGroupShift);   // per lane and operand
+  static constexpr int kRegs = P == sp::kF64 ? 4 : 16;
+  // which dword of the row's code string is dword j of the lane in group g
+  __device__ static constexpr int dword(int g, int j) {
+    return P == sp::kMxFp8 ? 8 * (j >> 2) + 4 * g + (j & 3) : g * kDwords + j;
+  }
+  __device__ static int idx(int lane) { return lane & ((1 << kGroupShift) - 1); }
+  __device__ static int group(int lane) { return lane >> kGroupShift; }
+  __device__ static int row(int lane, int reg) {
+    return P == sp::kF64 ? group(lane) + 4 * reg : (reg & 3) + 8 * (reg >> 2) + 4 * group(lane);
+  }
+};
+
+// One instruction of path P on the lane's packed operand dwords (plain C++ packing).
+template <int P, int OA, int OB>
+__device__ __forceinline__ typename AccOf<P>::type path_mfma(const uint32_t (&a)[8], const uint32_t (&b)[8], uint32_t sa,
+                                                             uint32_t sb, typename AccOf<P>::type c) {
+  if constexpr (P == sp::kF16) {
+    const u32x4v av = {a[0], a[1], a[2], a[3]}, bv = {b[0], b[1], b[2], b[3]};
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av), __builtin_bit_cast(f16x8, bv), c, 0, 0, 0);
+  } else if constexpr (P == sp::kFp8 || P == sp::kBf8) {
+    const long av = static_cast<long>((static_cast<uint64_t>(a[1]) << 32) | a[0]);
+    const long bv = static_cast<long>((static_cast<uint64_t>(b[1]) << 32) | b[0]);
+    if constexpr (P == sp::kFp8)
+      return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(av, bv, c, 0, 0, 0);
+    else
+      return __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(av, bv, c, 0, 0, 0);
+  } else if constexpr (P == sp::kI8) {
+    const i32x4 av = {int(a[0]), int(a[1]), int(a[2]), int(a[3])}, bv = {int(b[0]), int(b[1]), int(b[2]), int(b[3])};
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, c, 0, 0, 0);
+  } else if constexpr (sp::path_scaled(P)) {
+    const i32x8 av = {int(a[0]), int(a[1]), int(a[2]), int(a[3]), int(a[4]), int(a[5]), int(a[6]), int(a[7])};
+    const i32x8 bv = {int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(b[4]), int(b[5]), int(b[6]), int(b[7])};
+    constexpr int kFmt = sp::path_fmt_select(P);   // cbsz and blgp are immediates
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, kFmt, kFmt, OA, static_cast<int>(sa), OB,
+                                                           static_cast<int>(sb));
+  } else if constexpr (P == sp::kF32) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[0]), __uint_as_float(b[0]), c, 0, 0, 0);
+  } else {
+    static_assert(P == sp::kF64, "unknown path");
+    const double av = __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(a[1]) << 32) | a[0]));
+    const double bv = __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(b[1]) << 32) | b[0]));
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
+  }
+}
+
+// The accumulator's register `reg` as the 32-bit words the expected tile holds at `at`.
+template <int P>
+__device__ __forceinline__ bool acc_differs(const typename AccOf<P>::type& c, int reg, const uint32_t* __restrict__ tile,
+                                            int at, uint32_t flip) {
+  if constexpr (P == sp::kF64) {
+    const uint64_t got = static_cast<uint64_t>(__double_as_longlong(c[reg])) ^ flip;
+    return got != ((static_cast<uint64_t>(tile[2 * at + 1]) << 32) | tile[2 * at]);
+  } else if constexpr (P == sp::kI8) {
+    return (static_cast<uint32_t>(c[reg]) ^ flip) != tile[at];
+  } else {
+    return (__float_as_uint(c[reg]) ^ flip) != tile[at];
+  }
+}
+
+// One wave, one instruction on the caller's packed codes: A and B hold path_row_dwords(P)
+// dwords per row / column, SA and SB one scale dword per (row | column, k block). C is written
+// row-major in the expected tile's words (matrix_tile establishes the lane maps above).
+template <int P, int OA, int OB>
+__global__ __launch_bounds__(64) void matrix_tile_kernel(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B,
+                                                         const uint32_t* __restrict__ SA, const uint32_t* __restrict__ SB,
+                                                         uint32_t* __restrict__ C) {
+  using M = LaneMap<P>;
+  const int l = threadIdx.x, idx = M::idx(l), g = M::group(l);
+  uint32_t a[8] = {}, b[8] = {};
+#pragma unroll
+  for (int j = 0; j < M::kDwords; ++j) {
+    a[j] = A[idx * sp::path_row_dwords(P) + M::dword(g, j)];
+    b[j] = B[idx * sp::path_row_dwords(P) + M::dword(g, j)];
+  }
+  uint32_t sa = 0, sb = 0;
+  if constexpr (sp::path_scaled(P)) {
+    sa = SA[idx * 2 + g];
+    sb = SB[idx * 2 + g];
+  }
+  typename AccOf<P>::type c = {};
+  c = path_mfma<P, OA, OB>(a, b, sa, sb, c);
+  const int dim = sp::path_dim(P);
+#pragma unroll
+  for (int reg = 0; reg < M::kRegs; ++reg) {
+    const int at = M::row(l, reg) * dim + idx;
+    if constexpr (P == sp::kF64) {
+      const uint64_t v = static_cast<uint64_t>(__double_as_longlong(c[reg]));
+      C[2 * at] = static_cast<uint32_t>(v);
+      C[2 * at + 1] = static_cast<uint32_t>(v >> 32);
+    } else if constexpr (P == sp::kI8) {
+      C[at] = static_cast<uint32_t>(c[reg]);
+    } else {
+      C[at] = __float_as_uint(c[reg]);
+    }
+  }
+}
+
+template <int P, int S>
+__device__ __forceinline__ void path_step(int idx, int g, typename AccOf<P>::type& c) {
+  using M = LaneMap<P>;
+  uint32_t a[8] = {}, b[8] = {};
+#pragma unroll
+  for (int j = 0; j < M::kDwords; ++j) {
+    a[j] = sp::path_dword(P, 0, S, idx, M::dword(g, j));
+    b[j] = sp::path_dword(P, 1, S, idx, M::dword(g, j));
+  }
+  uint32_t sa = 0, sb = 0;
+  if constexpr (sp::path_scaled(P)) {
+    sa = sp::path_scale_dword(P, 0, S, idx, g);
+    sb = sp::path_scale_dword(P, 1, S, idx, g);
+  }
+  c = path_mfma<P, sp::path_opsel(0, S), sp::path_opsel(1, S)>(a, b, sa, sb, c);
+}
+
+// The chain of kPathSteps accumulating instructions of path P on this wave, compared bit for
+// bit with the host's tile (`tiles` + P * kTileWords; the sweep passes its copy in LDS). `flip` is the test hook's bit, XORed
+// into the value of register 0 before the comparison.
+template <int P>
+__device__ __forceinline__ bool path_chain_differs(int lane, const uint32_t* __restrict__ tiles, uint32_t flip) {
+  using M = LaneMap<P>;
+  static_assert(sp::kPathSteps == 8, "the chain is unrolled by hand: the scale byte selects are immediates");
+  const int idx = M::idx(lane), g = M::group(lane);
+  typename AccOf<P>::type c = {};
+  path_step<P, 0>(idx, g, c);
+  path_step<P, 1>(idx, g, c);
+  path_step<P, 2>(idx, g, c);
+  path_step<P, 3>(idx, g, c);
+  path_step<P, 4>(idx, g, c);
+  path_step<P, 5>(idx, g, c);
+  path_step<P, 6>(idx, g, c);
+  path_step<P, 7>(idx, g, c);
+  const uint32_t* tile = tiles + P * sp::kTileWords;
+  bool bad = false;
+#pragma unroll
+  for (int reg = 0; reg < M::kRegs; ++reg)
+    bad |= acc_differs<P>(c, reg, tile, M::row(lane, reg) * sp::path_dim(P) + idx, reg == 0 ? flip : 0u);
+  return bad;
+}
+
+template <int P>
+__device__ __forceinline__ uint32_t path_checked(uint32_t paths, int lane, const uint32_t* __restrict__ tiles,
+                                                 int inject_path) {
+  if (!(paths >> P & 1u)) return 0u;   // wave-uniform
+  return path_chain_differs<P>(lane, tiles, inject_path == P ? 1u : 0u) ? 1u << P : 0u;
+}
 
 // One visit of one CU: every wave runs the exact MFMA chain and compares its accumulators
 // bit for bit with the host's integer tile (C layout as in mfma_tile); the workgroup then
 // writes mix32(i ^ seed) over `n` LDS dwords, reads it back through other threads than the
 // writers, and repeats with the complement. One record per workgroup (selftest_host.h).
 // No spin, no inter-workgroup traffic; every loop is bounded by `n` or a constant.
+// kPaths: the visit also runs the chain of every path in `paths` on all four waves, against
+// `tiles` (kNumPaths x kTileWords words), and writes the 7-word record of selftest_paths_host.h.
+// The tiles are first staged in the LDS array, which the pattern test overwrites afterwards:
+// one round of global loads per workgroup, in flight during the bf16 chain, instead of one
+// round trip per path and wave (n >= kNumPaths * kTileWords is the host's to ensure).
+template <bool kPaths = false>
 __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const float* __restrict__ expected,
-                                           uint32_t* __restrict__ out, uint32_t seed, SweepInject inj) {
+                                           uint32_t* __restrict__ out, uint32_t seed, SweepInject inj,
+                                           uint32_t paths = 0, const uint32_t* __restrict__ tiles = nullptr) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   uint32_t xcc, hwid;
@@ -154,6 +342,13 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
   const bool mine = inj.kind != kInjectNone && xcc == static_cast<uint32_t>(inj.xcc) &&
                     st::hw_cu_key(hwid) == static_cast<uint32_t>(inj.cu_key);
+  constexpr uint32_t kStaged4 = sp::kNumPaths * sp::kTileWords / 4;
+  if constexpr (kPaths) {
+    const u32x4v* src = reinterpret_cast<const u32x4v*>(tiles);
+    u32x4v* dst = reinterpret_cast<u32x4v*>(lds);
+#pragma unroll
+    for (uint32_t i = 0; i < kStaged4 / kSweepBlock; ++i) dst[i * kSweepBlock + tid] = src[i * kSweepBlock + tid];
+  }
 
   f32x16 c = {};
 #pragma unroll
@@ -173,6 +368,22 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
     if (mine && inj.kind == kInjectMfma && tid == 0 && reg == 0) got ^= 1u;
     const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
     mfma_bad |= got != __float_as_uint(expected[row * 32 + r]);
+  }
+  uint32_t path_bad = 0;
+  if constexpr (kPaths) {
+    static_assert(kStaged4 % kSweepBlock == 0, "the staging loop has no tail");
+    __syncthreads();   // the tiles are in LDS
+    const int inject_path = mine && inj.kind == kInjectPath && tid == 0 ? static_cast<int>(inj.lds_off) : -1;
+    path_bad |= path_checked<sp::kF16>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kFp8>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kBf8>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kI8>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kMxFp8>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kMxFp6>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kMxFp4>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kF32>(paths, lane, lds, inject_path);
+    path_bad |= path_checked<sp::kF64>(paths, lane, lds, inject_path);
+    __syncthreads();   // every wave has compared before the pattern test overwrites the tiles
   }
 
   volatile uint32_t* v = lds;
@@ -195,9 +406,17 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
     lds[0] = 0;
     lds[1] = 0;
     lds[2] = st::kNoBadOffset;
+    if constexpr (kPaths) {
+      lds[3] = 0;
+      lds[4] = 0;
+    }
   }
   __syncthreads();
   if (mfma_bad) atomicOr(&lds[0], 1u << wave);
+  if (path_bad) {
+    atomicOr(&lds[3], path_bad);
+    atomicOr(&lds[4], 1u << wave);
+  }
   if (bad != st::kNoBadOffset) {
     atomicOr(&lds[0], st::kFailLds);
     atomicMin(&lds[2], bad);
@@ -205,12 +424,16 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
   if (lane == 0) atomicOr(&lds[1], 1u << st::hw_simd(hwid));
   __syncthreads();
   if (tid == 0) {
-    uint32_t* o = out + static_cast<size_t>(blockIdx.x) * st::kSweepRecordWords;
+    uint32_t* o = out + static_cast<size_t>(blockIdx.x) * (kPaths ? sp::kPathRecordWords : st::kSweepRecordWords);
     o[0] = xcc;
     o[1] = hwid;
     o[2] = lds[0];
     o[3] = lds[1];
     o[4] = lds[2];
+    if constexpr (kPaths) {
+      o[5] = lds[3];
+      o[6] = lds[4];
+    }
   }
 }
 
@@ -230,6 +453,23 @@ __global__ __launch_bounds__(kSweepBlock) void cu_sweep_part(const float* __rest
                                                              SweepInject inj, uint32_t n) {
   extern __shared__ uint32_t lds_dyn[];
   sweep_body(lds_dyn, n, expected, out, seed, inj);
+}
+
+// The same two kernels with the matrix paths' chains in every visit.
+__global__ __launch_bounds__(kSweepBlock) void cu_sweep_paths_full(const float* __restrict__ expected,
+                                                                   uint32_t* __restrict__ out, uint32_t seed,
+                                                                   SweepInject inj, uint32_t paths,
+                                                                   const uint32_t* __restrict__ tiles) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsDwordsFull];
+  sweep_body<true>(lds, kLdsDwordsFull, expected, out, seed, inj, paths, tiles);
+}
+
+__global__ __launch_bounds__(kSweepBlock) void cu_sweep_paths_part(const float* __restrict__ expected,
+                                                                   uint32_t* __restrict__ out, uint32_t seed,
+                                                                   SweepInject inj, uint32_t n, uint32_t paths,
+                                                                   const uint32_t* __restrict__ tiles) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn16[];
+  sweep_body<true>(lds_dyn16, n, expected, out, seed, inj, paths, tiles);
 }
 
 // HBM pattern test in hbm_copy's shape (256 threads, 4 x 16 B per thread in flight,
@@ -729,7 +969,8 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
 // ---------------------------------------------------------------------------- deep self-test (host)
 
 struct SweepResult {
-  std::vector<uint32_t> words;   // kSweepRecordWords per workgroup
+  std::vector<uint32_t> words;   // record_words per workgroup
+  int record_words = st::kSweepRecordWords;
   int blocks = 0;
   size_t lds_bytes = 0;
   double ms = 0.0;
@@ -737,7 +978,23 @@ struct SweepResult {
 
 // rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
 // hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
-SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj) {
+// `paths` != 0 launches the cu_sweep_paths kernels instead (same grid, block and LDS), with
+// every path's expected tile uploaded once, and returns their 7-word records.
+const std::vector<uint32_t>& path_tiles() {   // independent of seed and device: computed once
+  static const std::vector<uint32_t> tiles = [] {
+    std::vector<uint32_t> t(static_cast<size_t>(sp::kNumPaths) * sp::kTileWords);
+    for (int p = 0; p < sp::kNumPaths; ++p) {
+      const sp::PathTile tile = sp::path_expected(p);
+      if (!tile.exact()) throw std::logic_error(std::string("path ") + sp::path_name(p) + ": the chain is not exact");
+      sp::path_expected_words(p, tile, t.data() + static_cast<size_t>(p) * sp::kTileWords);
+    }
+    return t;
+  }();
+  return tiles;
+}
+
+SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj,
+                     uint32_t paths = 0) {
   HIP_OK(hipSetDevice(dev));
   if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
   int cus = 0;
@@ -751,7 +1008,9 @@ SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uin
 
   uint32_t n = kLdsDwordsFull;
   int fit = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0) != hipSuccess) {
+  if (paths & ~sp::kAllPaths) throw std::invalid_argument("cu_sweep_paths: unknown path bit");
+  if ((paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_full, kSweepBlock, 0)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0)) != hipSuccess) {
     (void)hipGetLastError();
     fit = 0;
   }
@@ -761,7 +1020,9 @@ SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uin
     HIP_OK(hipGetDeviceProperties(&p, dev));
     n = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
     fit = 0;
-    if (n < 4 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n * 4u) != hipSuccess ||
+    if (n < (paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u) ||
+        (paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_part, kSweepBlock, n * 4u)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n * 4u)) != hipSuccess ||
         fit < 1) {
       (void)hipGetLastError();
       throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
@@ -775,12 +1036,22 @@ SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uin
   std::vector<float> tile_f(tile.begin(), tile.end());
   DevBuf<float> expected(tile_f.size());
   HIP_OK(hipMemcpy(expected.p, tile_f.data(), tile_f.size() * sizeof(float), hipMemcpyHostToDevice));
-  const size_t words = static_cast<size_t>(res.blocks) * st::kSweepRecordWords;
+  res.record_words = paths ? sp::kPathRecordWords : st::kSweepRecordWords;
+  const size_t words = static_cast<size_t>(res.blocks) * res.record_words;
   DevBuf<uint32_t> out(words);
+  DevBuf<uint32_t> tiles(paths ? path_tiles().size() : 1);
+  if (paths)
+    HIP_OK(hipMemcpy(tiles.p, path_tiles().data(), path_tiles().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   Stream stream(mask);
   Events ev;
   auto launch = [&](int blocks, SweepInject j) {
-    if (full)
+    if (paths && full)
+      hipLaunchKernelGGL(cu_sweep_paths_full, dim3(blocks), dim3(kSweepBlock), 0, stream.s, expected.p, out.p, seed, j,
+                         paths, tiles.p);
+    else if (paths)
+      hipLaunchKernelGGL(cu_sweep_paths_part, dim3(blocks), dim3(kSweepBlock), n * 4u, stream.s, expected.p, out.p,
+                         seed, j, n, paths, tiles.p);
+    else if (full)
       hipLaunchKernelGGL(cu_sweep_full, dim3(blocks), dim3(kSweepBlock), 0, stream.s, expected.p, out.p, seed, j);
     else
       hipLaunchKernelGGL(cu_sweep_part, dim3(blocks), dim3(kSweepBlock), n * 4u, stream.s, expected.p, out.p, seed,
@@ -797,7 +1068,7 @@ SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uin
   res.words.resize(words);
   HIP_OK(hipMemcpy(res.words.data(), out.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (int b = 0; b < res.blocks; ++b)
-    if (!st::decode_record(res.words.data(), b).written())
+    if (!(paths ? sp::decode_path_record(res.words.data(), b).base : st::decode_record(res.words.data(), b)).written())
       throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
   return res;
 }
@@ -882,6 +1153,108 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   res.fill_gbs = moved / (fill_ms * 1e-3) / 1e9;
   res.verify_gbs = moved / (verify_ms * 1e-3) / 1e9;
   return res;
+}
+
+int path_index(const std::string& name) {
+  for (int p = 0; p < sp::kNumPaths; ++p)
+    if (name == sp::path_name(p)) return p;
+  throw std::invalid_argument("unknown matrix path '" + name + "'");
+}
+
+template <int P>
+void launch_tile(int opsel, const uint32_t* A, const uint32_t* B, const uint32_t* SA, const uint32_t* SB, uint32_t* C) {
+#define NANOGPU_TILE_CASE(I)                                                                                  \
+  case I:                                                                                                     \
+    hipLaunchKernelGGL((matrix_tile_kernel<P, (I) / 4, (I) % 4>), dim3(1), dim3(64), 0, 0, A, B, SA, SB, C); \
+    break;
+  if constexpr (sp::path_scaled(P)) {
+    switch (opsel) {   // the byte selects are immediates of the instruction
+      NANOGPU_TILE_CASE(0) NANOGPU_TILE_CASE(1) NANOGPU_TILE_CASE(2) NANOGPU_TILE_CASE(3)
+      NANOGPU_TILE_CASE(4) NANOGPU_TILE_CASE(5) NANOGPU_TILE_CASE(6) NANOGPU_TILE_CASE(7)
+      NANOGPU_TILE_CASE(8) NANOGPU_TILE_CASE(9) NANOGPU_TILE_CASE(10) NANOGPU_TILE_CASE(11)
+      NANOGPU_TILE_CASE(12) NANOGPU_TILE_CASE(13) NANOGPU_TILE_CASE(14) NANOGPU_TILE_CASE(15)
+    }
+  } else {
+    hipLaunchKernelGGL((matrix_tile_kernel<P, 0, 0>), dim3(1), dim3(64), 0, 0, A, B, SA, SB, C);
+  }
+#undef NANOGPU_TILE_CASE
+}
+
+// One instruction of path `p` on the caller's codes: a_codes is A[row][k] (dim x K, row-major),
+// b_codes is B[k][col] (K x dim), scale_a is [row][k block] and scale_b [k block][col] (E8M0,
+// scaled paths only), opsel_a / opsel_b the scale register's byte that carries them (the
+// other bytes get another scale). Returns the tile's words, row-major (path_expected_words).
+std::vector<uint32_t> matrix_tile(int p, const std::vector<uint64_t>& a_codes, const std::vector<uint64_t>& b_codes,
+                                  const std::vector<uint32_t>& scale_a, const std::vector<uint32_t>& scale_b,
+                                  int opsel_a, int opsel_b) {
+  const int dim = sp::path_dim(p), K = sp::path_k(p), cb = sp::path_code_bits(p), rowdw = sp::path_row_dwords(p);
+  const size_t n = static_cast<size_t>(dim) * K;
+  if (a_codes.size() != n || b_codes.size() != n)
+    throw std::invalid_argument("matrix_tile: A is dim x K codes and B is K x dim codes");
+  const size_t n_scale = sp::path_scaled(p) ? static_cast<size_t>(dim) * 2 : 0;
+  if (scale_a.size() != n_scale || scale_b.size() != n_scale)
+    throw std::invalid_argument("matrix_tile: scales are dim x 2 and 2 x dim on the scaled paths, absent elsewhere");
+  if (opsel_a < 0 || opsel_a > 3 || opsel_b < 0 || opsel_b > 3) throw std::invalid_argument("matrix_tile: opsel in 0..3");
+  std::vector<uint32_t> A(static_cast<size_t>(dim) * rowdw, 0u), B(A.size(), 0u), SA(dim * 2, 0u), SB(dim * 2, 0u);
+  auto put = [&](std::vector<uint32_t>& v, int idx, int k, uint64_t code) {
+    if (cb < 64 && (code >> cb)) throw std::invalid_argument("matrix_tile: a code wider than the format");
+    size_t bit = static_cast<size_t>(idx) * rowdw * 32 + static_cast<size_t>(k) * cb;
+    for (int i = 0; i < cb;) {
+      const int sh = static_cast<int>(bit % 32), take = std::min(cb - i, 32 - sh);
+      v[bit / 32] |= static_cast<uint32_t>((code >> i) & ((1ull << take) - 1)) << sh;
+      i += take;
+      bit += take;
+    }
+  };
+  for (int i = 0; i < dim; ++i)
+    for (int k = 0; k < K; ++k) {
+      put(A, i, k, a_codes[static_cast<size_t>(i) * K + k]);
+      put(B, i, k, b_codes[static_cast<size_t>(k) * dim + i]);
+    }
+  auto scale_dword = [](uint32_t scale, int byte) {
+    if (scale > 0xfe) throw std::invalid_argument("matrix_tile: an E8M0 scale is 0..254");
+    return ((scale ^ 1u) * 0x01010101u & ~(0xffu << (8 * byte))) | (scale << (8 * byte));
+  };
+  for (size_t i = 0; i < n_scale / 2; ++i)
+    for (int blk = 0; blk < 2; ++blk) {
+      SA[i * 2 + blk] = scale_dword(scale_a[i * 2 + blk], opsel_a);
+      SB[i * 2 + blk] = scale_dword(scale_b[static_cast<size_t>(blk) * dim + i], opsel_b);
+    }
+  DevBuf<uint32_t> da(A.size()), db(B.size()), dsa(SA.size()), dsb(SB.size()), dc(sp::kTileWords);
+  HIP_OK(hipMemcpy(da.p, A.data(), A.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(db.p, B.data(), B.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(dsa.p, SA.data(), SA.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(dsb.p, SB.data(), SB.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(dc.p, 0, sp::kTileWords * 4));
+  const int opsel = opsel_a * 4 + opsel_b;
+  switch (p) {
+    case sp::kF16: launch_tile<sp::kF16>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kFp8: launch_tile<sp::kFp8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kBf8: launch_tile<sp::kBf8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kI8: launch_tile<sp::kI8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kMxFp8: launch_tile<sp::kMxFp8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kMxFp6: launch_tile<sp::kMxFp6>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kMxFp4: launch_tile<sp::kMxFp4>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kF32: launch_tile<sp::kF32>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    case sp::kF64: launch_tile<sp::kF64>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
+    default: throw std::invalid_argument("matrix_tile: unknown path");
+  }
+  HIP_OK(hipGetLastError());
+  std::vector<uint32_t> c(sp::path_tile_words(p));
+  HIP_OK(hipMemcpy(c.data(), dc.p, c.size() * 4, hipMemcpyDeviceToHost));
+  return c;
+}
+
+SweepInject parse_path_inject(const py::object& inject) {
+  SweepInject inj{-1, -1, kInjectNone, 0};
+  if (inject.is_none()) return inj;
+  const py::tuple t = inject.cast<py::tuple>();
+  if (t.size() != 3) throw std::invalid_argument("cu_sweep_paths: inject = (xcc, cu_key, path name)");
+  inj.xcc = t[0].cast<int>();
+  inj.cu_key = t[1].cast<int>();
+  inj.kind = kInjectPath;
+  inj.lds_off = static_cast<uint32_t>(path_index(t[2].cast<std::string>()));
+  return inj;
 }
 
 SweepInject parse_inject(const py::object& inject) {
@@ -982,6 +1355,75 @@ PYBIND11_MODULE(_probe, m) {
       "exact bf16 MFMA chain on all 4 waves and a pattern test of the LDS. Records are (xcc, hw_id, fail bits, "
       "SIMD ids seen, first bad LDS dword or -1). inject = (xcc, cu_key, 'mfma' | 'lds'[, lds dword]) flips one "
       "bit of that CU's own data (tests).");
+  m.def(
+      "matrix_tile",
+      [](const std::string& path, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b,
+         const std::vector<uint32_t>& scale_a, const std::vector<uint32_t>& scale_b, std::pair<int, int> opsel) {
+        const int p = path_index(path);
+        const std::vector<uint32_t> w = matrix_tile(p, a, b, scale_a, scale_b, opsel.first, opsel.second);
+        py::list c;
+        const size_t n = static_cast<size_t>(sp::path_dim(p)) * sp::path_dim(p);
+        for (size_t i = 0; i < n; ++i) {
+          if (p == sp::kI8) {
+            c.append(static_cast<int32_t>(w[i]));
+          } else if (p == sp::kF64) {
+            const uint64_t bits = (static_cast<uint64_t>(w[2 * i + 1]) << 32) | w[2 * i];
+            double v;
+            std::memcpy(&v, &bits, 8);
+            c.append(v);
+          } else {
+            float v;
+            std::memcpy(&v, &w[i], 4);
+            c.append(v);
+          }
+        }
+        return c;
+      },
+      py::arg("path"), py::arg("a_codes"), py::arg("b_codes"), py::arg("scale_a") = std::vector<uint32_t>{},
+      py::arg("scale_b") = std::vector<uint32_t>{}, py::arg("opsel") = std::pair<int, int>{0, 0},
+      "One MFMA instruction of `path` (f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64) on operand codes: "
+      "a_codes = A[row][k] and b_codes = B[k][col] bit patterns, row-major; on the scaled paths scale_a = "
+      "[row][k block] and scale_b = [k block][col] E8M0 codes, carried in byte opsel = (a, b) of the scale "
+      "register. Returns C row-major: floats, ints for i8, doubles (16x16) for f64.");
+  m.def(
+      "cu_sweep_paths",
+      [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& paths,
+         const py::object& inject) {
+        uint32_t bits = 0;
+        for (const std::string& name : paths) bits |= 1u << path_index(name);
+        if (!bits) throw std::invalid_argument("cu_sweep_paths: no path selected");
+        const SweepInject inj = parse_path_inject(inject);
+        SweepResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = cu_sweep(dev, mask, rounds, seed, inj, bits);
+        }
+        py::list recs;
+        for (int b = 0; b < r.blocks; ++b) {
+          const sp::PathRecord rec = sp::decode_path_record(r.words.data(), b);
+          recs.append(py::make_tuple(rec.base.xcc, rec.base.hw_id, rec.base.fail, rec.base.simds,
+                                     rec.base.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.base.lds_bad),
+                                     rec.path_fail, rec.path_waves));
+        }
+        py::list names, checked;
+        for (int p = 0; p < sp::kNumPaths; ++p) {
+          names.append(sp::path_name(p));
+          if (bits >> p & 1u) checked.append(sp::path_name(p));
+        }
+        py::dict d;
+        d["records"] = recs;
+        d["paths"] = names;
+        d["checked"] = checked;
+        d["lds_bytes"] = r.lds_bytes;
+        d["ms"] = r.ms;
+        return d;
+      },
+      py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
+      py::arg("seed") = 0x5eed5eedu, py::arg("paths") = std::vector<std::string>{}, py::arg("inject") = py::none(),
+      "cu_sweep whose visits also run, on all 4 waves, an exact chain of 8 MFMA instructions of every path in "
+      "`paths` and compare every accumulator bit with the host's tile. Records are cu_sweep's 5 fields plus "
+      "(failed-path bits, waves that saw a path fail); `paths` in the result names the bits in order, `checked` "
+      "the paths that ran. inject = (xcc, cu_key, path name) flips one accumulator bit of that path on that CU (tests).");
   m.def(
       "hbm_pattern_check",
       [](int dev, size_t bytes, uint32_t seed, int passes, const std::vector<std::pair<uint64_t, uint32_t>>& corrupt,
