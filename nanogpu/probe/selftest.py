@@ -23,7 +23,9 @@ one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe.hip)
 What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
 and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache, and of
 the matrix unit the 16x16 shapes, the sparse (smfmac) forms, bf6 operands, mixed A / B formats
-and subnormal, Inf and NaN operands.
+and Inf and NaN operands. Zero, subnormal and largest-normal operands and E8M0 scales other than
+127 and 128 are outside the sweep's generators: `edge_tiles` puts them through `matrix_tile`, one
+wave on one CU, in the GPU tests only.
 
 `python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--json]` prints one report.
 """
@@ -285,8 +287,9 @@ def exact_product(path: str, a_codes, b_codes, scale_a=None, scale_b=None, acc=N
     sbt = None if scale_b is None else [[scale_b[blk][c] for blk in range(2)] for c in range(dim)]
     a, ea = _operand_ints(path, a_codes, scale_a)
     b, eb = _operand_ints(path, bt, sbt)
-    units = [[sum(x * y for x, y in zip(a[r], b[c])) for c in range(dim)] for r in range(dim)]
-    abs_units = [[sum(abs(x * y) for x, y in zip(a[r], b[c])) for c in range(dim)] for r in range(dim)]
+    nz = [[(k, y) for k, y in enumerate(col) if y] for col in b]      # a zero operand adds no term
+    units = [[sum(row[k] * y for k, y in col) for col in nz] for row in a]
+    abs_units = [[sum(abs(row[k] * y) for k, y in col) for col in nz] for row in a]
     return units, abs_units, ea + eb
 
 
@@ -407,6 +410,130 @@ def path_coverage(path: str) -> list[str]:
         if not any(path_opsel(op, s) for op in range(2) for s in range(PATH_STEPS)):
             unmet.add("opsel")
     return sorted(unmet)
+
+
+# ---- edge tiles: every operand code and every scale on the device, one term per accumulator ------
+#
+# The generators above stay inside an exponent window so that a chain of 8 instructions is exact
+# in any order. A tile in which every accumulator has at most one non-zero term is exact whatever
+# its codes, so these tiles hold what the window excludes: zero, subnormals, the largest normals,
+# every code of the narrow formats and every E8M0 scale. One operand ("codes") holds the codes
+# under test, the other ("units") a single +-1 per row or column (i8: -128 as well), at k =
+# edge_kmap. They are inputs of `matrix_tile` (tests/test_gpu_selftest_edges.py) and are not part
+# of the sweep.
+
+EDGE_ROTATIONS = (0, 5)          # two placements of the units' k on the unscaled paths
+EDGE_SCALE_TILES = 256           # scaled paths: 64 groups of scales x the 4 bytes of the scale register
+EDGE_SCALE_SUM = (-2, 2)         # scale_a + scale_b - 254 of every (row, col, block) of a tile
+
+
+def unit_codes(path: str) -> list[int]:
+    """The codes of +1 and -1 (i8: and -128) that meet the codes under test."""
+    if path == "i8":
+        return [0x01, 0xFF, 0x80]
+    _ebits, mbits, bias = PATH_FORMAT[path]
+    one = bias << mbits
+    return [one, one | 1 << (PATH_CODE_BITS[path] - 1)]
+
+
+def code_is_finite(path: str, code: int) -> bool:
+    """False for e4m3's S.1111.111 (NaN) and for an all-ones exponent field of e5m2, f16, f32 and
+    f64 (Inf, NaN). e2m3, e2m1 and i8 have only finite codes."""
+    if path in ("fp8", "mxfp8"):
+        return code & 0x7F != 0x7F
+    if path in ("bf8", "f16", "f32", "f64"):
+        ebits, mbits, _bias = PATH_FORMAT[path]
+        return (code >> mbits) & ((1 << ebits) - 1) != (1 << ebits) - 1
+    return True
+
+
+def edge_code_groups(path: str) -> list[list[int]]:
+    """The codes the edge tiles of `path` put on the device, in groups that share a tile.
+    Narrow formats: one group of all 2^bits codes, a non-finite one replaced by 0 (NaN x 0 would
+    make its whole row NaN). f16 / f32 / f64: +-0 with, by magnitude, the smallest and largest
+    subnormal and the smallest normal; 1, 1 + ulp and 2 - ulp; the largest finite value and the
+    largest power of two. The codes of one group share the exponent of their last place, so the
+    integers of `exact_product` stay small enough to convert to a float (f64 spans 2^2098)."""
+    ebits, mbits, bias = PATH_FORMAT[path]
+    bits = PATH_CODE_BITS[path]
+    if path not in ("f16", "f32", "f64"):
+        return [[c if code_is_finite(path, c) else 0 for c in range(1 << bits)]]
+    ones, top = (1 << mbits) - 1, ((1 << ebits) - 2) << mbits
+    groups = ([1, ones, 1 << mbits], [bias << mbits, bias << mbits | 1, bias << mbits | ones], [top | ones, top])
+    sign = 1 << (bits - 1)
+    return [[c | s for c in [0] + g for s in (0, sign)] for g in groups]
+
+
+def edge_kmap(path: str, i: int, rot: int) -> int:
+    """The one k at which row (units in A) or column (units in B) i of the units operand is
+    non-zero. K <= dim: (i + rot) mod K. The scaled paths (K = 64, dim = 32) take k block
+    (i >> 1) & 1, so that both blocks and both parities of i meet in every tile."""
+    dim, K = path_dim(path), PATH_K[path]
+    if K <= dim:
+        return (i + rot) % K
+    return (i + rot) % dim + dim * ((i >> 1) & 1)
+
+
+def edge_tile(path: str, codes, side: int, rot: int = 0, offset: int = 0):
+    """(a, b): a[row][k] and b[k][col]. side 0: `codes`, cyclically from `offset`, fill A at every
+    k some column's unit sits at, and B holds the units; side 1: the codes fill B, the units A.
+    Everything else is 0, so accumulator (row, col) has the one term at k = edge_kmap of its
+    units index."""
+    dim, K = path_dim(path), PATH_K[path]
+    units = unit_codes(path)
+    kmap = [edge_kmap(path, i, rot) for i in range(dim)]
+    image = sorted(set(kmap))
+    held = [[0] * K for _ in range(dim)]          # the codes operand, by its own index (row | col) and k
+    n = offset
+    for j in range(dim):
+        for k in image:
+            held[j][k] = codes[n % len(codes)]
+            n += 1
+    unit = [[0] * K for _ in range(dim)]
+    for i in range(dim):
+        unit[i][kmap[i]] = units[(i + (i >> 2)) % len(units)]
+    a, bt = (held, unit) if side == 0 else (unit, held)
+    return a, [[bt[c][k] for c in range(dim)] for k in range(K)]
+
+
+def edge_scales(path: str, t: int):
+    """(scale_a[row][block], scale_b[block][col], opsel) of scaled tile t (0..EDGE_SCALE_TILES-1).
+    Block b of group q = t // 4 has s0 = min(4 q + 2 b, 253); A's scales are s0 + (row & 1), B's
+    254 - s0 - (col & 1): scale_a + scale_b - 254 is -1, 0 or 1 for every (row, col, block), and
+    over the groups A and B each take every value 0..254. t % 4 is A's byte of the scale
+    register, (t % 4 + q) % 4 B's: every value meets every byte on both sides."""
+    dim = path_dim(path)
+    q, byte = divmod(t, 4)
+    s0 = [min(4 * q + 2 * b, 253) for b in range(2)]
+    sa = [[s0[b] + (r & 1) for b in range(2)] for r in range(dim)]
+    sb = [[254 - s0[b] - (c & 1) for c in range(dim)] for b in range(2)]
+    return sa, sb, (byte, (byte + q) % 4)
+
+
+def edge_tiles(path: str):
+    """Yields (a, b, scale_a, scale_b, opsel) of every edge tile of `path` (scales None and opsel
+    (0, 0) on the unscaled paths). Unscaled: every group of edge_code_groups on both sides at both
+    EDGE_ROTATIONS. Scaled: EDGE_SCALE_TILES tiles, the side alternating, each holding every code
+    of the format (1,024 slots) under its own scales, rotation and offset."""
+    groups = edge_code_groups(path)
+    if path not in SCALED_PATHS:
+        for g, codes in enumerate(groups):
+            for side in range(2):
+                for rot in EDGE_ROTATIONS:
+                    a, b = edge_tile(path, codes, side, rot, 3 * rot + g)
+                    yield a, b, None, None, (0, 0)
+        return
+    for t in range(EDGE_SCALE_TILES):
+        sa, sb, opsel = edge_scales(path, t)
+        a, b = edge_tile(path, groups[0], (t + t // 4) & 1, t % 32, 37 * t)
+        yield a, b, sa, sb, opsel
+
+
+def product_words(path: str, a, b, scale_a=None, scale_b=None) -> list[int]:
+    """The words `matrix_tile` must return for one exact instruction: exact_product as the
+    accumulator holds it. An accumulator whose only term is -0 holds +0."""
+    units, _abs, unit_exp = exact_product(path, a, b, scale_a, scale_b)
+    return tile_words(path, tile_values(path, [u for row in units for u in row], unit_exp))
 
 
 def fold_paths(records, paths, expected_cus) -> dict:

@@ -639,19 +639,53 @@ py::dict device_props(int dev) {
   return d;
 }
 
-bool copy_check(int dev, size_t n_floats) {
+// Test hook of copy_check and hbm_pattern_check: the buffer a kernel writes sits between two
+// guard regions of `guard_bytes` each, filled with kGuardByte before the launch and read back
+// after it. A multiple of 16 bytes, so the buffer keeps its 16-byte alignment.
+constexpr unsigned char kGuardByte = 0xA5;
+constexpr size_t kGuardMax = size_t(1) << 20;
+
+void check_guard_bytes(size_t guard_bytes) {
+  if (guard_bytes % 16 != 0 || guard_bytes > kGuardMax)
+    throw std::invalid_argument("guard_bytes: a multiple of 16, at most 1 MiB");
+}
+
+// Guard bytes that no longer hold kGuardByte, in the regions before and after `bytes` at `base + guard`.
+size_t guard_bytes_changed(const unsigned char* base, size_t guard, size_t bytes) {
+  if (guard == 0) return 0;
+  std::vector<unsigned char> g(2 * guard);
+  HIP_OK(hipMemcpy(g.data(), base, guard, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(g.data() + guard, base + guard + bytes, guard, hipMemcpyDeviceToHost));
+  return static_cast<size_t>(std::count_if(g.begin(), g.end(), [](unsigned char c) { return c != kGuardByte; }));
+}
+
+struct CopyCheck {
+  bool ok = false;              // destination == source, bit for bit
+  size_t guard_changed = 0;     // guard bytes the kernel overwrote
+};
+
+// The source holds integers below 1000003 as floats: the top byte of each is 0x00 or 0x3f..0x49,
+// never kGuardByte, so no element of the source written over a guard leaves it unchanged.
+CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
   HIP_OK(hipSetDevice(dev));
+  check_guard_bytes(guard_bytes);
   const size_t n4 = (n_floats + 3) / 4;
   std::vector<float> h(n4 * 4);
   for (size_t i = 0; i < h.size(); ++i) h[i] = static_cast<float>((i * 2654435761u) % 1000003u);
-  DevBuf<float4> a(n4), b(n4);
+  DevBuf<float4> a(n4);
+  DevBuf<unsigned char> b(n4 * 16 + 2 * guard_bytes);
+  float4* dst = reinterpret_cast<float4*>(b.p + guard_bytes);
   HIP_OK(hipMemcpy(a.p, h.data(), n4 * 16, hipMemcpyHostToDevice));
-  HIP_OK(hipMemset(b.p, 0, n4 * 16));
-  hipLaunchKernelGGL(hbm_copy, dim3(copy_grid(n4)), dim3(kCopyBlock), 0, 0, a.p, b.p, n4);
+  if (guard_bytes) HIP_OK(hipMemset(b.p, kGuardByte, n4 * 16 + 2 * guard_bytes));
+  HIP_OK(hipMemset(dst, 0, n4 * 16));
+  hipLaunchKernelGGL(hbm_copy, dim3(copy_grid(n4)), dim3(kCopyBlock), 0, 0, a.p, dst, n4);
   HIP_OK(hipGetLastError());
   std::vector<float> out(n4 * 4);
-  HIP_OK(hipMemcpy(out.data(), b.p, n4 * 16, hipMemcpyDeviceToHost));
-  return std::memcmp(out.data(), h.data(), n4 * 16) == 0;
+  HIP_OK(hipMemcpy(out.data(), dst, n4 * 16, hipMemcpyDeviceToHost));
+  CopyCheck res;
+  res.ok = std::memcmp(out.data(), h.data(), n4 * 16) == 0;
+  res.guard_changed = guard_bytes_changed(b.p, guard_bytes, n4 * 16);
+  return res;
 }
 
 double hbm_bandwidth(int dev, size_t bytes, int iters) {
@@ -976,10 +1010,6 @@ struct SweepResult {
   double ms = 0.0;
 };
 
-// rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
-// hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
-// `paths` != 0 launches the cu_sweep_paths kernels instead (same grid, block and LDS), with
-// every path's expected tile uploaded once, and returns their 7-word records.
 const std::vector<uint32_t>& path_tiles() {   // independent of seed and device: computed once
   static const std::vector<uint32_t> tiles = [] {
     std::vector<uint32_t> t(static_cast<size_t>(sp::kNumPaths) * sp::kTileWords);
@@ -993,84 +1023,191 @@ const std::vector<uint32_t>& path_tiles() {   // independent of seed and device:
   return tiles;
 }
 
-SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj,
-                     uint32_t paths = 0) {
-  HIP_OK(hipSetDevice(dev));
-  if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
-  int cus = 0;
-  if (mask.empty())
-    cus = cu_count(dev);
-  else
-    for (uint32_t w : mask) cus += __builtin_popcount(w);
-  if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep: the mask enables no CU");
-  SweepResult res;
-  res.blocks = rounds * cus;
+// Test hook: one word of the expected data, XORed on its way to the device. `tile` is -1 (none),
+// 0 (the bf16 chain's tile) or 1 + p (path p's tile). The word goes into the session's own
+// upload; the cached path_tiles() are never written.
+struct ExpectedFlip {
+  int tile = -1;
+  uint32_t word = 0, mask = 0;
+};
 
-  uint32_t n = kLdsDwordsFull;
-  int fit = 0;
-  if (paths & ~sp::kAllPaths) throw std::invalid_argument("cu_sweep_paths: unknown path bit");
-  if ((paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_full, kSweepBlock, 0)
-             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0)) != hipSuccess) {
-    (void)hipGetLastError();
-    fit = 0;
-  }
-  const bool full = fit >= 1;
-  if (!full) {
-    hipDeviceProp_t p;
-    HIP_OK(hipGetDeviceProperties(&p, dev));
-    n = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
-    fit = 0;
-    if (n < (paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u) ||
-        (paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_part, kSweepBlock, n * 4u)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n * 4u)) != hipSuccess ||
-        fit < 1) {
+// rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
+// hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
+// `paths` != 0 launches the cu_sweep_paths kernels instead (same grid, block and LDS), with
+// every path's expected tile uploaded once, and returns their 7-word records.
+// The session holds the buffers, the stream and the kernel choice, made once; `run` launches
+// and reads back. cu_sweep is one session and one run, sweep_sensitivity a run per word.
+class SweepSession {
+ public:
+  SweepSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t paths) : paths_(paths), stream_(mask) {
+    if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
+    int cus = 0;
+    if (mask.empty())
+      cus = cu_count(dev);
+    else
+      for (uint32_t w : mask) cus += __builtin_popcount(w);
+    if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep: the mask enables no CU");
+    blocks_ = rounds * cus;
+
+    int fit = 0;
+    if (paths & ~sp::kAllPaths) throw std::invalid_argument("cu_sweep_paths: unknown path bit");
+    if ((paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_full, kSweepBlock, 0)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0)) != hipSuccess) {
       (void)hipGetLastError();
-      throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
+      fit = 0;
+    }
+    full_ = fit >= 1;
+    if (!full_) {
+      hipDeviceProp_t p;
+      HIP_OK(hipGetDeviceProperties(&p, dev));
+      n_ = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
+      fit = 0;
+      if (n_ < (paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u) ||
+          (paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_part, kSweepBlock, n_ * 4u)
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n_ * 4u)) != hipSuccess ||
+          fit < 1) {
+        (void)hipGetLastError();
+        throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
+      }
+    }
+
+    std::vector<int32_t> tile(32 * 32);
+    st::sweep_expected(tile.data());
+    expected_host_.assign(tile.begin(), tile.end());
+    expected_.reset(new DevBuf<float>(expected_host_.size()));
+    HIP_OK(hipMemcpy(expected_->p, expected_host_.data(), expected_host_.size() * sizeof(float), hipMemcpyHostToDevice));
+    record_words_ = paths ? sp::kPathRecordWords : st::kSweepRecordWords;
+    out_.reset(new DevBuf<uint32_t>(static_cast<size_t>(blocks_) * record_words_));
+    tiles_.reset(new DevBuf<uint32_t>(paths ? path_tiles().size() : 1));
+    if (paths)
+      HIP_OK(hipMemcpy(tiles_->p, path_tiles().data(), path_tiles().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    launch(1, 0u, SweepInject{-1, -1, kInjectNone, 0});   // loads the code object outside the timed span
+  }
+
+  // Puts the device's expected data back as the host computed it, then XORs `f`'s word. The
+  // stream is idle between runs (run() synchronises), so plain copies are ordered with it.
+  void set_flip(const ExpectedFlip& f) {
+    if (flip_.tile >= 0) write_word(flip_, 0u);
+    flip_ = ExpectedFlip{};
+    if (f.tile < 0) return;
+    if (f.tile > sp::kNumPaths) throw std::invalid_argument("corrupt_expected: unknown tile");
+    if (f.tile > 0 && !(paths_ >> (f.tile - 1) & 1u))
+      throw std::invalid_argument(std::string("corrupt_expected: path ") + sp::path_name(f.tile - 1) + " is not selected");
+    const uint32_t words = f.tile == 0 ? 32u * 32u : static_cast<uint32_t>(sp::path_tile_words(f.tile - 1));
+    if (f.word >= words) throw std::invalid_argument("corrupt_expected: word beyond the tile");
+    write_word(f, f.mask);
+    flip_ = f;
+  }
+
+  SweepResult run(uint32_t seed, SweepInject inj) {
+    if (inj.kind == kInjectLds && inj.lds_off >= n_) throw std::invalid_argument("cu_sweep: inject offset beyond the LDS array");
+    SweepResult res;
+    res.blocks = blocks_;
+    res.lds_bytes = static_cast<size_t>(n_) * 4;
+    res.record_words = record_words_;
+    const size_t words = static_cast<size_t>(blocks_) * record_words_;
+    HIP_OK(hipMemsetAsync(out_->p, 0xff, words * sizeof(uint32_t), stream_.s));
+    HIP_OK(hipEventRecord(ev_.a, stream_.s));
+    launch(blocks_, seed, inj);
+    HIP_OK(hipEventRecord(ev_.b, stream_.s));
+    res.ms = ev_.ms();
+    HIP_OK(hipStreamSynchronize(stream_.s));
+    res.words.resize(words);
+    HIP_OK(hipMemcpy(res.words.data(), out_->p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < blocks_; ++b)
+      if (!(paths_ ? sp::decode_path_record(res.words.data(), b).base : st::decode_record(res.words.data(), b)).written())
+        throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
+    return res;
+  }
+
+ private:
+  void write_word(const ExpectedFlip& f, uint32_t mask) {
+    uint32_t w;
+    if (f.tile == 0) {
+      std::memcpy(&w, &expected_host_[f.word], 4);
+      w ^= mask;
+      HIP_OK(hipMemcpy(reinterpret_cast<uint32_t*>(expected_->p) + f.word, &w, 4, hipMemcpyHostToDevice));
+    } else {
+      const size_t at = static_cast<size_t>(f.tile - 1) * sp::kTileWords + f.word;
+      w = path_tiles()[at] ^ mask;
+      HIP_OK(hipMemcpy(tiles_->p + at, &w, 4, hipMemcpyHostToDevice));
     }
   }
-  res.lds_bytes = static_cast<size_t>(n) * 4;
-  if (inj.kind == kInjectLds && inj.lds_off >= n) throw std::invalid_argument("cu_sweep: inject offset beyond the LDS array");
 
-  std::vector<int32_t> tile(32 * 32);
-  st::sweep_expected(tile.data());
-  std::vector<float> tile_f(tile.begin(), tile.end());
-  DevBuf<float> expected(tile_f.size());
-  HIP_OK(hipMemcpy(expected.p, tile_f.data(), tile_f.size() * sizeof(float), hipMemcpyHostToDevice));
-  res.record_words = paths ? sp::kPathRecordWords : st::kSweepRecordWords;
-  const size_t words = static_cast<size_t>(res.blocks) * res.record_words;
-  DevBuf<uint32_t> out(words);
-  DevBuf<uint32_t> tiles(paths ? path_tiles().size() : 1);
-  if (paths)
-    HIP_OK(hipMemcpy(tiles.p, path_tiles().data(), path_tiles().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  Stream stream(mask);
-  Events ev;
-  auto launch = [&](int blocks, SweepInject j) {
-    if (paths && full)
-      hipLaunchKernelGGL(cu_sweep_paths_full, dim3(blocks), dim3(kSweepBlock), 0, stream.s, expected.p, out.p, seed, j,
-                         paths, tiles.p);
-    else if (paths)
-      hipLaunchKernelGGL(cu_sweep_paths_part, dim3(blocks), dim3(kSweepBlock), n * 4u, stream.s, expected.p, out.p,
-                         seed, j, n, paths, tiles.p);
-    else if (full)
-      hipLaunchKernelGGL(cu_sweep_full, dim3(blocks), dim3(kSweepBlock), 0, stream.s, expected.p, out.p, seed, j);
+  void launch(int blocks, uint32_t seed, SweepInject j) {
+    if (paths_ && full_)
+      hipLaunchKernelGGL(cu_sweep_paths_full, dim3(blocks), dim3(kSweepBlock), 0, stream_.s, expected_->p, out_->p, seed, j,
+                         paths_, tiles_->p);
+    else if (paths_)
+      hipLaunchKernelGGL(cu_sweep_paths_part, dim3(blocks), dim3(kSweepBlock), n_ * 4u, stream_.s, expected_->p, out_->p,
+                         seed, j, n_, paths_, tiles_->p);
+    else if (full_)
+      hipLaunchKernelGGL(cu_sweep_full, dim3(blocks), dim3(kSweepBlock), 0, stream_.s, expected_->p, out_->p, seed, j);
     else
-      hipLaunchKernelGGL(cu_sweep_part, dim3(blocks), dim3(kSweepBlock), n * 4u, stream.s, expected.p, out.p, seed,
-                         j, n);
+      hipLaunchKernelGGL(cu_sweep_part, dim3(blocks), dim3(kSweepBlock), n_ * 4u, stream_.s, expected_->p, out_->p, seed,
+                         j, n_);
     HIP_OK(hipGetLastError());
-  };
-  launch(1, SweepInject{-1, -1, kInjectNone, 0});   // loads the code object outside the timed span
-  HIP_OK(hipMemsetAsync(out.p, 0xff, words * sizeof(uint32_t), stream.s));
-  HIP_OK(hipEventRecord(ev.a, stream.s));
-  launch(res.blocks, inj);
-  HIP_OK(hipEventRecord(ev.b, stream.s));
-  res.ms = ev.ms();
-  HIP_OK(hipStreamSynchronize(stream.s));
-  res.words.resize(words);
-  HIP_OK(hipMemcpy(res.words.data(), out.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (int b = 0; b < res.blocks; ++b)
-    if (!(paths ? sp::decode_path_record(res.words.data(), b).base : st::decode_record(res.words.data(), b)).written())
-      throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
-  return res;
+  }
+
+  uint32_t paths_;
+  Stream stream_;
+  Events ev_;
+  int blocks_ = 0, record_words_ = st::kSweepRecordWords;
+  uint32_t n_ = kLdsDwordsFull;
+  bool full_ = false;
+  ExpectedFlip flip_;
+  std::vector<float> expected_host_;
+  std::unique_ptr<DevBuf<float>> expected_;
+  std::unique_ptr<DevBuf<uint32_t>> out_, tiles_;
+};
+
+SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj,
+                     uint32_t paths = 0, ExpectedFlip flip = {}) {
+  HIP_OK(hipSetDevice(dev));
+  SweepSession session(dev, mask, rounds, paths);
+  session.set_flip(flip);
+  return session.run(seed, inj);
+}
+
+// Test hook behind tests/test_gpu_selftest_sensitivity.py: for every (word, xor mask) of tile
+// `tile` (ExpectedFlip's numbering) one sweep of `rounds` rounds with that word of the expected
+// data corrupted, on one session. Per word the AND and the OR over all records of the fields
+// fail, lds_bad, path_fail and path_waves (the last two 0 when `paths` is 0): 8 words, AND first.
+struct Sensitivity {
+  std::vector<uint32_t> fields;   // 8 per word
+  int records = 0;                // per sweep
+  double seconds = 0.0;           // wall time of the loop
+};
+
+Sensitivity sweep_sensitivity(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, uint32_t paths,
+                              int tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips) {
+  HIP_OK(hipSetDevice(dev));
+  if (flips.size() > 4096) throw std::invalid_argument("sweep_sensitivity: at most 4096 words a call");
+  SweepSession session(dev, mask, rounds, paths);
+  Sensitivity out;
+  out.fields.reserve(flips.size() * 8);
+  const Clock::time_point t0 = Clock::now();
+  for (const auto& f : flips) {
+    session.set_flip(ExpectedFlip{tile, f.first, f.second});
+    const SweepResult r = session.run(seed, SweepInject{-1, -1, kInjectNone, 0});
+    out.records = r.blocks;
+    uint32_t a[4] = {~0u, ~0u, ~0u, ~0u}, o[4] = {0, 0, 0, 0};
+    for (int b = 0; b < r.blocks; ++b) {
+      uint32_t v[4] = {0, 0, 0, 0};
+      if (paths) {
+        const sp::PathRecord rec = sp::decode_path_record(r.words.data(), b);
+        v[0] = rec.base.fail, v[1] = rec.base.lds_bad, v[2] = rec.path_fail, v[3] = rec.path_waves;
+      } else {
+        const st::SweepRecord rec = st::decode_record(r.words.data(), b);
+        v[0] = rec.fail, v[1] = rec.lds_bad;
+      }
+      for (int i = 0; i < 4; ++i) a[i] &= v[i], o[i] |= v[i];
+    }
+    out.fields.insert(out.fields.end(), a, a + 4);
+    out.fields.insert(out.fields.end(), o, o + 4);
+  }
+  out.seconds = std::chrono::duration<double>(Clock::now() - t0).count();
+  return out;
 }
 
 struct PatternResult {
@@ -1078,25 +1215,30 @@ struct PatternResult {
   unsigned long long errors = 0;
   std::vector<st::Mismatch> first;
   double fill_gbs = 0.0, verify_gbs = 0.0;
+  size_t guard_changed = 0;   // guard bytes overwritten (guard_bytes > 0 only)
 };
 
 // Fill `bytes` of fresh device memory with the address-derived pattern and verify it, `passes`
 // times (odd passes: the complement). `corrupt` = (byte offset, xor byte) pairs the host applies
-// between a pass's fill and its verify; `verify_seed` < 0 verifies with `seed`.
+// between a pass's fill and its verify; `verify_seed` < 0 verifies with `seed`. `guard_bytes`
+// (tests) puts the buffer between two guard regions, see kGuardByte.
 PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes,
-                                const std::vector<std::pair<uint64_t, uint32_t>>& corrupt, int64_t verify_seed) {
+                                const std::vector<std::pair<uint64_t, uint32_t>>& corrupt, int64_t verify_seed,
+                                size_t guard_bytes) {
   HIP_OK(hipSetDevice(dev));
+  check_guard_bytes(guard_bytes);
   if (bytes == 0 || bytes % 16 != 0) throw std::invalid_argument("hbm_pattern_check: bytes must be a positive multiple of 16");
   if (passes < 1 || passes > 16) throw std::invalid_argument("hbm_pattern_check: passes in 1..16");
   for (const auto& c : corrupt)
-    if (c.first >= bytes || c.second > 0xff) throw std::invalid_argument("hbm_pattern_check: corrupt = (offset < bytes, xor byte)");
+    if (c.first >= bytes + guard_bytes || c.second > 0xff)   // with a guard, the guard behind the buffer too
+      throw std::invalid_argument("hbm_pattern_check: corrupt = (offset < bytes, xor byte)");
   const size_t n = bytes / 16;
   if ((n + kCopyBlock * kCopyUnroll - 1) / (kCopyBlock * kCopyUnroll) > 0x7fffffffull)   // gridDim.x
     throw std::invalid_argument("hbm_pattern_check: too large for one launch");
   const uint32_t vseed = verify_seed < 0 ? seed : static_cast<uint32_t>(verify_seed);
 
   struct Buf {   // an allocation that does not fit is the caller's to shrink, not a device fault
-    u32x4* p = nullptr;
+    unsigned char* p = nullptr;
     explicit Buf(size_t b) {
       const hipError_t e = hipMalloc(&p, b);
       if (e == hipErrorOutOfMemory) {
@@ -1108,33 +1250,39 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
     ~Buf() {
       if (p) (void)hipFree(p);
     }
-  } buf(bytes);
+  } whole(bytes + 2 * guard_bytes);
+  u32x4* const data = reinterpret_cast<u32x4*>(whole.p + guard_bytes);
+  if (guard_bytes) {
+    HIP_OK(hipMemset(whole.p, kGuardByte, guard_bytes));
+    HIP_OK(hipMemset(whole.p + guard_bytes + bytes, kGuardByte, guard_bytes));
+    HIP_OK(hipDeviceSynchronize());   // the kernels run on a stream that does not wait for the null stream
+  }
   DevBuf<VerifyOut> vo(1);
   Stream stream({});
   Events ev;
   HIP_OK(hipMemsetAsync(vo.p, 0, sizeof(VerifyOut), stream.s));
   // n = 0 touches no memory: loads both kernels outside the timed spans
-  hipLaunchKernelGGL(hbm_fill, dim3(1), dim3(kCopyBlock), 0, stream.s, buf.p, size_t(0), seed, 0u);
-  hipLaunchKernelGGL(hbm_verify, dim3(1), dim3(kCopyBlock), 0, stream.s, buf.p, size_t(0), seed, 0u, vo.p);
+  hipLaunchKernelGGL(hbm_fill, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), seed, 0u);
+  hipLaunchKernelGGL(hbm_verify, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), seed, 0u, vo.p);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(stream.s));
   const dim3 grid(copy_grid(n));
   double fill_ms = 0.0, verify_ms = 0.0;
   for (int pass = 0; pass < passes; ++pass) {
     HIP_OK(hipEventRecord(ev.a, stream.s));
-    hipLaunchKernelGGL(hbm_fill, grid, dim3(kCopyBlock), 0, stream.s, buf.p, n, seed, static_cast<uint32_t>(pass));
+    hipLaunchKernelGGL(hbm_fill, grid, dim3(kCopyBlock), 0, stream.s, data, n, seed, static_cast<uint32_t>(pass));
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ev.b, stream.s));
     fill_ms += ev.ms();
     for (const auto& c : corrupt) {
-      unsigned char* at = reinterpret_cast<unsigned char*>(buf.p) + c.first;
+      unsigned char* at = reinterpret_cast<unsigned char*>(data) + c.first;
       unsigned char byte = 0;
       HIP_OK(hipMemcpy(&byte, at, 1, hipMemcpyDeviceToHost));
       byte ^= static_cast<unsigned char>(c.second);
       HIP_OK(hipMemcpy(at, &byte, 1, hipMemcpyHostToDevice));
     }
     HIP_OK(hipEventRecord(ev.a, stream.s));
-    hipLaunchKernelGGL(hbm_verify, grid, dim3(kCopyBlock), 0, stream.s, buf.p, n, vseed, static_cast<uint32_t>(pass), vo.p);
+    hipLaunchKernelGGL(hbm_verify, grid, dim3(kCopyBlock), 0, stream.s, data, n, vseed, static_cast<uint32_t>(pass), vo.p);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ev.b, stream.s));
     verify_ms += ev.ms();
@@ -1152,6 +1300,7 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   const double moved = static_cast<double>(bytes) * passes;
   res.fill_gbs = moved / (fill_ms * 1e-3) / 1e9;
   res.verify_gbs = moved / (verify_ms * 1e-3) / 1e9;
+  res.guard_changed = guard_bytes_changed(whole.p, guard_bytes, bytes);
   return res;
 }
 
@@ -1275,6 +1424,23 @@ SweepInject parse_inject(const py::object& inject) {
   return inj;
 }
 
+// "bf16" is tile 0, path p's tile 1 + p (ExpectedFlip).
+int tile_index(const std::string& name) { return name == "bf16" ? 0 : 1 + path_index(name); }
+
+// corrupt_expected of cu_sweep: (word, xor); of cu_sweep_paths: (tile name, word, xor).
+ExpectedFlip parse_flip(const py::object& corrupt, bool named) {
+  ExpectedFlip f;
+  if (corrupt.is_none()) return f;
+  const py::tuple t = corrupt.cast<py::tuple>();
+  if (t.size() != (named ? 3u : 2u))
+    throw std::invalid_argument(named ? "cu_sweep_paths: corrupt_expected = ('bf16' | path name, word, xor)"
+                                      : "cu_sweep: corrupt_expected = (word, xor)");
+  f.tile = named ? tile_index(t[0].cast<std::string>()) : 0;
+  f.word = t[named ? 1 : 0].cast<uint32_t>();
+  f.mask = t[named ? 2 : 1].cast<uint32_t>();
+  return f;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_probe, m) {
@@ -1296,8 +1462,25 @@ PYBIND11_MODULE(_probe, m) {
         "bf16 MFMA TFLOP/s on a CU-masked stream.");
   m.def("gemm_tile", &gemm_tile, py::arg("a"), py::arg("b"),
         "C[32x32] = bf16(A[32x16]) @ bf16(B[16x32]) with one v_mfma_f32_32x32x16_bf16 (fp32 accumulate).");
-  m.def("copy_check", &copy_check, py::arg("device") = 0, py::arg("n_floats") = size_t(1) << 24,
-        py::call_guard<py::gil_scoped_release>(), "hbm_copy kernel result == source, bit for bit.");
+  m.def(
+      "copy_check",
+      [](int dev, size_t n_floats, size_t guard_bytes) -> py::object {
+        CopyCheck r;
+        {
+          py::gil_scoped_release nogil;
+          r = copy_check(dev, n_floats, guard_bytes);
+        }
+        if (guard_bytes == 0) return py::bool_(r.ok);
+        py::dict d;
+        d["ok"] = r.ok;
+        d["guards_ok"] = r.guard_changed == 0;
+        d["guard_bytes_changed"] = r.guard_changed;
+        return d;
+      },
+      py::arg("device") = 0, py::arg("n_floats") = size_t(1) << 24, py::arg("guard_bytes") = size_t(0),
+      "hbm_copy kernel result == source, bit for bit. Test hook: guard_bytes > 0 (a multiple of 16) puts the "
+      "destination between two guard regions of that size and returns {ok, guards_ok, guard_bytes_changed} "
+      "instead of the bool: guards_ok is false when the kernel wrote outside the destination.");
   m.def("mixed_colocated", &mixed_colocated, py::arg("device"), py::arg("hbm_mask"), py::arg("mfma_mask"),
         py::arg("bytes") = size_t(1) << 30, py::arg("iters") = 10, py::arg("mfma_blocks") = 1536,
         py::arg("mfma_iters") = 4096, py::call_guard<py::gil_scoped_release>(),
@@ -1330,12 +1513,14 @@ PYBIND11_MODULE(_probe, m) {
   py::register_exception<PeerTimeout>(m, "PeerTimeout", PyExc_TimeoutError);
   m.def(
       "cu_sweep",
-      [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const py::object& inject) {
+      [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const py::object& inject,
+         const py::object& corrupt_expected) {
         const SweepInject inj = parse_inject(inject);
+        const ExpectedFlip flip = parse_flip(corrupt_expected, false);
         SweepResult r;
         {
           py::gil_scoped_release nogil;
-          r = cu_sweep(dev, mask, rounds, seed, inj);
+          r = cu_sweep(dev, mask, rounds, seed, inj, 0, flip);
         }
         py::list recs;
         for (int b = 0; b < r.blocks; ++b) {
@@ -1350,11 +1535,12 @@ PYBIND11_MODULE(_probe, m) {
         return d;
       },
       py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
-      py::arg("seed") = 0x5eed5eedu, py::arg("inject") = py::none(),
+      py::arg("seed") = 0x5eed5eedu, py::arg("inject") = py::none(), py::arg("corrupt_expected") = py::none(),
       "Deep CU check on a CU-masked stream: rounds x CUs workgroups, each holding a CU's whole LDS, run an "
       "exact bf16 MFMA chain on all 4 waves and a pattern test of the LDS. Records are (xcc, hw_id, fail bits, "
       "SIMD ids seen, first bad LDS dword or -1). inject = (xcc, cu_key, 'mfma' | 'lds'[, lds dword]) flips one "
-      "bit of that CU's own data (tests).");
+      "bit of that CU's own data (tests). Test hook: corrupt_expected = (word, xor) XORs word 0..1023 of the host's "
+      "expected bf16 tile in the upload, so every wave of every visit must report the MFMA check failed.");
   m.def(
       "matrix_tile",
       [](const std::string& path, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b,
@@ -1388,15 +1574,16 @@ PYBIND11_MODULE(_probe, m) {
   m.def(
       "cu_sweep_paths",
       [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& paths,
-         const py::object& inject) {
+         const py::object& inject, const py::object& corrupt_expected) {
         uint32_t bits = 0;
         for (const std::string& name : paths) bits |= 1u << path_index(name);
         if (!bits) throw std::invalid_argument("cu_sweep_paths: no path selected");
         const SweepInject inj = parse_path_inject(inject);
+        const ExpectedFlip flip = parse_flip(corrupt_expected, true);
         SweepResult r;
         {
           py::gil_scoped_release nogil;
-          r = cu_sweep(dev, mask, rounds, seed, inj, bits);
+          r = cu_sweep(dev, mask, rounds, seed, inj, bits, flip);
         }
         py::list recs;
         for (int b = 0; b < r.blocks; ++b) {
@@ -1420,19 +1607,52 @@ PYBIND11_MODULE(_probe, m) {
       },
       py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
       py::arg("seed") = 0x5eed5eedu, py::arg("paths") = std::vector<std::string>{}, py::arg("inject") = py::none(),
+      py::arg("corrupt_expected") = py::none(),
       "cu_sweep whose visits also run, on all 4 waves, an exact chain of 8 MFMA instructions of every path in "
       "`paths` and compare every accumulator bit with the host's tile. Records are cu_sweep's 5 fields plus "
       "(failed-path bits, waves that saw a path fail); `paths` in the result names the bits in order, `checked` "
-      "the paths that ran. inject = (xcc, cu_key, path name) flips one accumulator bit of that path on that CU (tests).");
+      "the paths that ran. inject = (xcc, cu_key, path name) flips one accumulator bit of that path on that CU (tests). "
+      "Test hook: corrupt_expected = ('bf16' | path name, word, xor) XORs one word of that expected tile (1024 "
+      "words, f64 512) in this call's upload, never in the host's cached tiles; the path must be selected.");
+  m.def(
+      "sweep_sensitivity",
+      [](int dev, const std::string& tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
+         const std::vector<std::string>& paths, const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
+        uint32_t bits = 0;
+        for (const std::string& name : paths) bits |= 1u << path_index(name);
+        const int t = tile_index(tile);
+        Sensitivity r;
+        {
+          py::gil_scoped_release nogil;
+          r = sweep_sensitivity(dev, mask, rounds, seed, bits, t, flips);
+        }
+        py::list words;
+        for (size_t i = 0; i < flips.size(); ++i) {
+          const uint32_t* f = r.fields.data() + 8 * i;
+          auto off = [](uint32_t v) { return v == st::kNoBadOffset ? int64_t(-1) : int64_t(v); };
+          words.append(py::make_tuple(py::make_tuple(f[0], off(f[1]), f[2], f[3]), py::make_tuple(f[4], off(f[5]), f[6], f[7])));
+        }
+        py::dict d;
+        d["words"] = words;
+        d["records"] = r.records;
+        d["seconds"] = r.seconds;
+        return d;
+      },
+      py::arg("device"), py::arg("tile"), py::arg("flips"), py::arg("paths") = std::vector<std::string>{},
+      py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 1, py::arg("seed") = 0x5eed5eedu,
+      "Test hook: for every (word, xor) of `flips` one sweep (cu_sweep_paths over `paths`, or cu_sweep when "
+      "`paths` is empty) with that word of expected tile `tile` ('bf16' or a path name) corrupted as by "
+      "corrupt_expected, all on one set of buffers. words[i] = (AND, OR) over that sweep's records of (fail bits, "
+      "lds_bad or -1, failed-path bits, path waves); records = workgroups per sweep, seconds = the loop's wall time.");
   m.def(
       "hbm_pattern_check",
       [](int dev, size_t bytes, uint32_t seed, int passes, const std::vector<std::pair<uint64_t, uint32_t>>& corrupt,
-         const py::object& verify_seed) {
+         const py::object& verify_seed, size_t guard_bytes) {
         const int64_t vseed = verify_seed.is_none() ? int64_t(-1) : int64_t(verify_seed.cast<uint32_t>());
         PatternResult r;
         {
           py::gil_scoped_release nogil;
-          r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed);
+          r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed, guard_bytes);
         }
         py::list first;
         for (const st::Mismatch& mm : r.first)
@@ -1443,15 +1663,18 @@ PYBIND11_MODULE(_probe, m) {
         d["first"] = first;
         d["fill_gbs"] = r.fill_gbs;
         d["verify_gbs"] = r.verify_gbs;
+        if (guard_bytes) d["guard_ok"] = r.guard_changed == 0;
         return d;
       },
       py::arg("device") = 0, py::arg("bytes") = size_t(256) << 20, py::arg("seed") = 0x5eed5eedu,
       py::arg("passes") = 2, py::arg("corrupt") = std::vector<std::pair<uint64_t, uint32_t>>{},
-      py::arg("verify_seed") = py::none(),
+      py::arg("verify_seed") = py::none(), py::arg("guard_bytes") = size_t(0),
       "Fills `bytes` of device memory with an address-derived pattern and verifies it (odd passes: the "
       "complement). errors counts mismatching 16-byte elements over all passes; first = up to 16 of "
       "(byte offset of the first differing byte, expected word, got word). corrupt = [(byte offset, xor byte)] "
-      "is applied by the host between fill and verify. Raises MemoryError when the buffer cannot be allocated.");
+      "is applied by the host between fill and verify. Test hook: guard_bytes > 0 (a multiple of 16) puts the "
+      "buffer between two guard regions of that size and adds guard_ok, false when a guard byte changed: a kernel "
+      "wrote outside the buffer, or `corrupt` named an offset in the guard behind it (bytes <= offset < bytes + guard_bytes). Raises MemoryError when the buffer cannot be allocated.");
   m.def(
       "mem_info",
       [](int dev) {

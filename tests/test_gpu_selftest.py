@@ -88,16 +88,41 @@ def test_injected_mfma_fault_fails_exactly_that_cu(P, clean):
     assert rep["failed"] == [{"xcc": 3, "cu_key": key, "kinds": ["mfma"], "lds_bad_off": -1}], rep["failed"]
 
 
-@pytest.mark.parametrize("where", ["last", "first"])
+# The read-back visits dword n - 1 - j with a stride of 256 threads: besides the two ends, the
+# last dword of the first stride and the first of the second (255, 256), the middle, and the
+# same two counted from the end (n - 256, n - 257) are where an index slip would hide.
+LDS_OFFSETS = {"last": lambda n: n - 1, "first": lambda n: 0, "255": lambda n: 255, "256": lambda n: 256,
+               "half": lambda n: n // 2, "n-256": lambda n: n - 256, "n-257": lambda n: n - 257}
+
+
+@pytest.mark.parametrize("where", list(LDS_OFFSETS))
 def test_injected_lds_fault_reports_the_offset(P, clean, where):
     from nanogpu.probe.selftest import fold_sweep
 
     key = _a_cu_on_xcd3(clean[0]["records"])
-    last = clean[0]["lds_bytes"] // 4 - 1       # 40959 when the workgroup holds all 160 KiB
-    off = last if where == "last" else 0
+    n = clean[0]["lds_bytes"] // 4              # 40960 when the workgroup holds all 160 KiB
+    off = LDS_OFFSETS[where](n)
     r = P.cu_sweep(0, [], 8, SEED, (3, key, "lds", off))
     rep = fold_sweep(r["records"], 256)
     assert rep["failed"] == [{"xcc": 3, "cu_key": key, "kinds": ["lds"], "lds_bad_off": off}], rep["failed"]
+
+
+def test_two_injected_cus_fold_to_two_cus_with_their_own_offsets(P, clean):
+    """Two runs, each with one CU injected at its own LDS dword, folded together: fold_sweep
+    keeps both CUs and gives each the offset that was put into it."""
+    from nanogpu.probe.selftest import cu_key, fold_sweep
+
+    n = clean[0]["lds_bytes"] // 4
+    keys5 = sorted({cu_key(h) for x, h, *_ in clean[0]["records"] if x == 5})
+    first = (3, _a_cu_on_xcd3(clean[0]["records"]), n - 257)
+    second = (5, keys5[-1], 256)
+    records = []
+    for xcc, key, off in (first, second):
+        records += list(P.cu_sweep(0, [], 8, SEED, (xcc, key, "lds", off))["records"])
+    rep = fold_sweep(records, 256)
+    assert rep["failed"] == [{"xcc": xcc, "cu_key": key, "kinds": ["lds"], "lds_bad_off": off}
+                             for xcc, key, off in (first, second)], rep["failed"]
+    assert rep["cus_seen"] == 256
 
 
 # 16 B: the tail path alone; one short of 4096 elements, and 4096; the same around the kernel's own
@@ -170,3 +195,55 @@ def test_deep_selftest_and_agent_on_the_real_device(P):
     assert failed == [], failed
     if agent.selftest_stats:
         assert 'nanogpu_selftest_cus_checked{device="0"} 256' in render(topo, selftest=agent.selftest_stats)
+
+
+# ----------------------------------------------------------------------------- bounds and small sizes
+GUARD = 4096
+
+# float4 counts around the fast path's test `base + 3 * 256 < n` (n = 768 + 1 is the first size
+# at which thread 0 takes it), around one thread block's 256 threads and one block's 1,024
+# elements, two blocks and a bit, and many blocks plus a 3-element tail
+COPY_COUNTS = [1, 255, 256, 257, 767, 768, 769, 1023, 1024, 1025, 2049, (1 << 20) + 3]
+
+
+@pytest.mark.parametrize("n4", COPY_COUNTS)
+def test_copy_writes_the_destination_and_nothing_around_it(P, n4):
+    r = P.copy_check(0, 4 * n4, GUARD)
+    assert r == {"ok": True, "guards_ok": True, "guard_bytes_changed": 0}, (n4, r)
+
+
+def test_copy_check_without_a_guard_is_still_a_bool_and_a_guard_is_whole_elements(P):
+    assert P.copy_check(0, 4 * 769) is True
+    assert P.copy_check(0, 4 * 769, 0) is True
+    with pytest.raises(ValueError):
+        P.copy_check(0, 4 * 769, 4097)
+    assert "guard_ok" not in P.hbm_pattern_check(0, 16, SEED, 1)
+
+
+@pytest.mark.parametrize("nbytes", [16, 4096 * 16 - 16, 4096 * 16, 1024 * 16 - 16, 1024 * 16, 1024 * 16 + 16, BIG])
+def test_pattern_fill_writes_the_buffer_and_nothing_around_it(P, nbytes):
+    r = P.hbm_pattern_check(0, nbytes, SEED, 2, [], None, GUARD)
+    assert r["bytes"] == nbytes and r["errors"] == 0 and r["first"] == [], r
+    assert r["guard_ok"] is True
+
+
+def test_a_changed_guard_byte_is_reported(P):
+    """The guard check itself can fail: with a guard, `corrupt` may address the guard behind
+    the buffer (one pass: a second pass would flip the byte back)."""
+    nbytes = 1024 * 16 + 16
+    for off in (nbytes, nbytes + GUARD - 1):
+        r = P.hbm_pattern_check(0, nbytes, SEED, 1, [(off, 0x01)], None, GUARD)
+        assert r["errors"] == 0 and r["guard_ok"] is False, (off, r)
+    with pytest.raises(ValueError):
+        P.hbm_pattern_check(0, nbytes, SEED, 1, [(nbytes + GUARD, 0x01)], None, GUARD)
+    with pytest.raises(ValueError):
+        P.hbm_pattern_check(0, nbytes, SEED, 1, [(nbytes, 0x01)])
+
+
+def test_pattern_check_wrong_seed_counts_every_element_of_a_tail(P):
+    """3 full blocks and 5 elements: the last block takes hbm_verify's tail path for all of its
+    threads, and the tail must count, not merely run."""
+    n = 3 * 1024 + 5
+    r = P.hbm_pattern_check(0, n * 16, SEED, 1, [], SEED + 1, GUARD)
+    assert r["errors"] == n, r["errors"]
+    assert len(r["first"]) == 16 and r["guard_ok"] is True
