@@ -84,6 +84,16 @@ def fail_kinds(fail_bits: int) -> list[str]:
     return kinds
 
 
+def _coverage(seen, expected_cus) -> tuple[int, list, int]:
+    """(n_expected, uncovered, n_uncovered) of the CU keys in `seen` against `expected_cus`: a set
+    of `(xcc, cu_key)`, or only their number (then `uncovered` cannot be listed and is empty)."""
+    if isinstance(expected_cus, int):
+        return expected_cus, [], max(0, expected_cus - len(seen))
+    expected = {tuple(k) for k in expected_cus}
+    uncovered = sorted(expected - set(seen))
+    return len(expected), uncovered, len(uncovered)
+
+
 def fold_sweep(records, expected_cus) -> dict:
     """Folds `cu_sweep` records `(xcc, hw_id, fail_bits, simds, lds_bad_off)` by CU.
 
@@ -99,14 +109,7 @@ def fold_sweep(records, expected_cus) -> dict:
         c["simds"] |= simds
         if bad >= 0 and (c["bad"] < 0 or bad < c["bad"]):
             c["bad"] = bad
-    if isinstance(expected_cus, int):
-        n_expected, uncovered = expected_cus, []
-        n_uncovered = max(0, n_expected - len(seen))
-    else:
-        expected = {tuple(k) for k in expected_cus}
-        n_expected = len(expected)
-        uncovered = sorted(expected - set(seen))
-        n_uncovered = len(uncovered)
+    n_expected, uncovered, n_uncovered = _coverage(seen, expected_cus)
     per_xcd: dict[int, int] = {}
     for xcc, _ in seen:
         per_xcd[xcc] = per_xcd.get(xcc, 0) + 1
@@ -548,14 +551,7 @@ def fold_paths(records, paths, expected_cus) -> dict:
         c = seen.setdefault((xcc, cu_key(hw_id)), [0, 0])
         c[0] |= pfail
         c[1] |= pwaves
-    if isinstance(expected_cus, int):
-        n_expected, uncovered = expected_cus, []
-        n_uncovered = max(0, n_expected - len(seen))
-    else:
-        expected = {tuple(k) for k in expected_cus}
-        n_expected = len(expected)
-        uncovered = sorted(expected - set(seen))
-        n_uncovered = len(uncovered)
+    n_expected, uncovered, n_uncovered = _coverage(seen, expected_cus)
 
     def names(bits: int) -> list[str]:
         out = [paths[i] for i in range(len(paths)) if bits >> i & 1]

@@ -11,10 +11,11 @@
 //                   must scale with the CUs granted);
 //   * hbm_copy    — streaming HBM3E bandwidth (16 B/lane, grid >> 256 WGs);
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
-//   * cu_sweep, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA pipes
-//                   and LDS, and free HBM against an address-derived pattern.
-//   * matrix_tile, cu_sweep_paths — the same sweep over the rest of the matrix unit: f16,
-//                   fp8 / bf8, i8, block-scaled fp8 / fp6 / fp4, f32 and f64 MFMA.
+//   * cu_sweep_kernel, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA
+//                   pipes and LDS (`cu_sweep`), and free HBM against an address-derived pattern.
+//   * matrix_tile_kernel, cu_sweep_kernel<kPaths> — the same sweep over the rest of the matrix
+//                   unit (`cu_sweep_paths`): f16, fp8 / bf8, i8, block-scaled fp8 / fp6 / fp4,
+//                   f32 and f64 MFMA.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
@@ -26,9 +27,11 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "nanogpu/selftest_host.h"
@@ -137,11 +140,12 @@ constexpr int kSweepBlock = 256;               // 4 waves: one per SIMD's MFMA p
 constexpr uint32_t kLdsDwordsFull = 40960;     // 160 KiB: the whole LDS of a gfx950 CU
 enum : int { kInjectNone = 0, kInjectMfma = 1, kInjectLds = 2, kInjectPath = 3 };
 
-// Test hook: the workgroup running on CU (xcc, cu_key) flips one bit of data it owns
-// (kInjectPath: of path `lds_off`'s accumulator, in cu_sweep_paths only).
+// Test hook: the workgroup running on CU (xcc, cu_key) flips one bit of data it owns: of the
+// bf16 accumulator, of LDS dword `lds_off`, or of path `path`'s accumulator (cu_sweep_paths only).
 struct SweepInject {
-  int xcc, cu_key, kind;
-  uint32_t lds_off;
+  int xcc = -1, cu_key = -1, kind = kInjectNone;
+  uint32_t lds_off = 0;
+  int path = -1;
 };
 
 // ---- matrix paths (selftest_paths_host.h) ----
@@ -321,6 +325,17 @@ __device__ __forceinline__ uint32_t path_checked(uint32_t paths, int lane, const
   return path_chain_differs<P>(lane, tiles, inject_path == P ? 1u : 0u) ? 1u << P : 0u;
 }
 
+using AllPaths = std::make_integer_sequence<int, sp::kNumPaths>;   // the one list of the paths
+
+// Bit P is set when selected path P's chain differed; the chains run in index order.
+template <int... P>
+__device__ __forceinline__ uint32_t paths_checked(std::integer_sequence<int, P...>, uint32_t paths, int lane,
+                                                  const uint32_t* __restrict__ tiles, int inject_path) {
+  uint32_t bad = 0;
+  ((bad |= path_checked<P>(paths, lane, tiles, inject_path)), ...);
+  return bad;
+}
+
 // One visit of one CU: every wave runs the exact MFMA chain and compares its accumulators
 // bit for bit with the host's integer tile (C layout as in mfma_tile); the workgroup then
 // writes mix32(i ^ seed) over `n` LDS dwords, reads it back through other threads than the
@@ -331,10 +346,10 @@ __device__ __forceinline__ uint32_t path_checked(uint32_t paths, int lane, const
 // The tiles are first staged in the LDS array, which the pattern test overwrites afterwards:
 // one round of global loads per workgroup, in flight during the bf16 chain, instead of one
 // round trip per path and wave (n >= kNumPaths * kTileWords is the host's to ensure).
-template <bool kPaths = false>
+template <bool kPaths>
 __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const float* __restrict__ expected,
                                            uint32_t* __restrict__ out, uint32_t seed, SweepInject inj,
-                                           uint32_t paths = 0, const uint32_t* __restrict__ tiles = nullptr) {
+                                           uint32_t paths, const uint32_t* __restrict__ tiles) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   uint32_t xcc, hwid;
@@ -373,16 +388,8 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
   if constexpr (kPaths) {
     static_assert(kStaged4 % kSweepBlock == 0, "the staging loop has no tail");
     __syncthreads();   // the tiles are in LDS
-    const int inject_path = mine && inj.kind == kInjectPath && tid == 0 ? static_cast<int>(inj.lds_off) : -1;
-    path_bad |= path_checked<sp::kF16>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kFp8>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kBf8>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kI8>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kMxFp8>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kMxFp6>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kMxFp4>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kF32>(paths, lane, lds, inject_path);
-    path_bad |= path_checked<sp::kF64>(paths, lane, lds, inject_path);
+    const int inject_path = mine && inj.kind == kInjectPath && tid == 0 ? inj.path : -1;
+    path_bad = paths_checked(AllPaths{}, paths, lane, lds, inject_path);
     __syncthreads();   // every wave has compared before the pattern test overwrites the tiles
   }
 
@@ -437,39 +444,23 @@ __device__ __forceinline__ void sweep_body(uint32_t* lds, uint32_t n, const floa
   }
 }
 
-// Holds all 160 KiB, so at most one sweep workgroup is resident per CU and a grid of
-// rounds x CUs workgroups is spread over every enabled CU by the dispatcher.
-__global__ __launch_bounds__(kSweepBlock) void cu_sweep_full(const float* __restrict__ expected,
-                                                             uint32_t* __restrict__ out, uint32_t seed,
-                                                             SweepInject inj) {
-  __shared__ uint32_t lds[kLdsDwordsFull];
-  sweep_body(lds, kLdsDwordsFull, expected, out, seed, inj);
-}
-
-// For a runtime that does not let one block hold a whole CU's LDS: `n` dwords of dynamic
-// LDS, sized by the host to sharedMemPerBlock.
-__global__ __launch_bounds__(kSweepBlock) void cu_sweep_part(const float* __restrict__ expected,
-                                                             uint32_t* __restrict__ out, uint32_t seed,
-                                                             SweepInject inj, uint32_t n) {
-  extern __shared__ uint32_t lds_dyn[];
-  sweep_body(lds_dyn, n, expected, out, seed, inj);
-}
-
-// The same two kernels with the matrix paths' chains in every visit.
-__global__ __launch_bounds__(kSweepBlock) void cu_sweep_paths_full(const float* __restrict__ expected,
-                                                                   uint32_t* __restrict__ out, uint32_t seed,
-                                                                   SweepInject inj, uint32_t paths,
-                                                                   const uint32_t* __restrict__ tiles) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsDwordsFull];
-  sweep_body<true>(lds, kLdsDwordsFull, expected, out, seed, inj, paths, tiles);
-}
-
-__global__ __launch_bounds__(kSweepBlock) void cu_sweep_paths_part(const float* __restrict__ expected,
-                                                                   uint32_t* __restrict__ out, uint32_t seed,
-                                                                   SweepInject inj, uint32_t n, uint32_t paths,
-                                                                   const uint32_t* __restrict__ tiles) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn16[];
-  sweep_body<true>(lds_dyn16, n, expected, out, seed, inj, paths, tiles);
+// kFull: the block holds all 160 KiB, so at most one sweep workgroup is resident per CU and a
+// grid of rounds x CUs workgroups is spread over every enabled CU by the dispatcher. Otherwise
+// (a runtime that does not let one block hold a whole CU's LDS, or the lds_bytes test hook) `n`
+// dwords of dynamic LDS, sized by the host. The plain instantiations ignore `paths` and `tiles`.
+// Both arrays are 16-byte aligned for the staging loop.
+template <bool kPaths, bool kFull>
+__global__ __launch_bounds__(kSweepBlock) void cu_sweep_kernel(const float* __restrict__ expected,
+                                                               uint32_t* __restrict__ out, uint32_t seed,
+                                                               SweepInject inj, uint32_t n, uint32_t paths,
+                                                               const uint32_t* __restrict__ tiles) {
+  if constexpr (kFull) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsDwordsFull];
+    sweep_body<kPaths>(lds, kLdsDwordsFull, expected, out, seed, inj, paths, tiles);
+  } else {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
+    sweep_body<kPaths>(lds_dyn, n, expected, out, seed, inj, paths, tiles);
+  }
 }
 
 // HBM pattern test in hbm_copy's shape (256 threads, 4 x 16 B per thread in flight,
@@ -545,26 +536,39 @@ uint16_t f32_to_bf16_bits(float f) {  // round to nearest even
   return static_cast<uint16_t>(u >> 16);
 }
 
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  explicit DevBuf(size_t n) { HIP_OK(hipMalloc(&p, n * sizeof(T))); }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// mfma_burn: 4 chains a wave, 4 waves a block, 32768 FLOP an instruction.
+double burn_tflops(int blocks, int iters, double ms) {
+  return 4.0 * 32768.0 * iters * (static_cast<double>(blocks) * 4) / (ms * 1e-3) / 1e12;
+}
+
+// hbm_copy of n float4, `iters` times: read + write bytes.
+double copy_gbs(size_t n, int iters, double ms) {
+  return 2.0 * static_cast<double>(n * sizeof(float4)) * iters / (ms * 1e-3) / 1e9;
+}
+
 std::vector<float> gemm_tile(const std::vector<float>& a, const std::vector<float>& b) {
   if (a.size() != 32 * 16 || b.size() != 16 * 32) throw std::invalid_argument("gemm_tile: A is 32x16, B is 16x32");
   std::vector<uint16_t> ha(a.size()), hb(b.size());
   for (size_t i = 0; i < a.size(); ++i) ha[i] = f32_to_bf16_bits(a[i]);
   for (size_t i = 0; i < b.size(); ++i) hb[i] = f32_to_bf16_bits(b[i]);
-  uint16_t *da = nullptr, *db = nullptr;
-  float* dc = nullptr;
-  HIP_OK(hipMalloc(&da, ha.size() * 2));
-  HIP_OK(hipMalloc(&db, hb.size() * 2));
-  HIP_OK(hipMalloc(&dc, 32 * 32 * 4));
-  HIP_OK(hipMemcpy(da, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(db, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_tile, dim3(1), dim3(64), 0, 0, reinterpret_cast<const __bf16*>(da),
-                     reinterpret_cast<const __bf16*>(db), dc);
+  DevBuf<uint16_t> da(ha.size()), db(hb.size());
+  DevBuf<float> dc(32 * 32);
+  HIP_OK(hipMemcpy(da.p, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(db.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(mfma_tile, dim3(1), dim3(64), 0, 0, reinterpret_cast<const __bf16*>(da.p),
+                     reinterpret_cast<const __bf16*>(db.p), dc.p);
   HIP_OK(hipGetLastError());
   std::vector<float> c(32 * 32);
-  HIP_OK(hipMemcpy(c.data(), dc, c.size() * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dc);
+  HIP_OK(hipMemcpy(c.data(), dc.p, c.size() * 4, hipMemcpyDeviceToHost));
   return c;
 }
 
@@ -596,15 +600,6 @@ struct Events {
     float t = 0.f;
     HIP_OK(hipEventElapsedTime(&t, a, b));
     return t;
-  }
-};
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t n) { HIP_OK(hipMalloc(&p, n * sizeof(T))); }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
   }
 };
 
@@ -704,8 +699,7 @@ double hbm_bandwidth(int dev, size_t bytes, int iters) {
     hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev.b, st.s));
-  const double ms = ev.ms();
-  return 2.0 * static_cast<double>(n * sizeof(float4)) * iters / (ms * 1e-3) / 1e9;  // GB/s, read+write
+  return copy_gbs(n, iters, ev.ms());
 }
 
 py::list census(int dev, const std::vector<uint32_t>& mask, int blocks, int sleep_iters) {
@@ -724,27 +718,7 @@ py::list census(int dev, const std::vector<uint32_t>& mask, int blocks, int slee
   return res;
 }
 
-double mfma_ms_impl(int dev, const std::vector<uint32_t>& mask, int blocks, int iters);
-inline double mfma_ms(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
-  return mfma_ms_impl(dev, mask, blocks, iters);
-}
-
-py::dict mfma_throughput(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
-  double ms = 0.0;
-  {
-    py::gil_scoped_release nogil;  // device work without the GIL; py objects built after
-    ms = mfma_ms(dev, mask, blocks, iters);
-  }
-  const double flop = 4.0 * 32768.0 * iters * (static_cast<double>(blocks) * 256 / 64);
-  py::dict d;
-  d["ms"] = ms;
-  d["tflops"] = flop / (ms * 1e-3) / 1e12;
-  d["blocks"] = blocks;
-  d["iters"] = iters;
-  return d;
-}
-
-double mfma_ms_impl(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
+double mfma_ms(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
   HIP_OK(hipSetDevice(dev));
   if (blocks <= 0 || iters <= 0) throw std::invalid_argument("mfma_throughput: bad shape");
   DevBuf<float> out(static_cast<size_t>(blocks) * 256);
@@ -757,6 +731,20 @@ double mfma_ms_impl(int dev, const std::vector<uint32_t>& mask, int blocks, int 
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev.b, st.s));
   return ev.ms();
+}
+
+py::dict mfma_throughput(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
+  double ms = 0.0;
+  {
+    py::gil_scoped_release nogil;  // device work without the GIL; py objects built after
+    ms = mfma_ms(dev, mask, blocks, iters);
+  }
+  py::dict d;
+  d["ms"] = ms;
+  d["tflops"] = burn_tflops(blocks, iters, ms);
+  d["blocks"] = blocks;
+  d["iters"] = iters;
+  return d;
 }
 
 // Co-located tenants: one MFMA burn per CU mask, each on its own CU-masked stream, all
@@ -789,10 +777,7 @@ std::vector<double> mfma_colocated(int dev, const std::vector<std::vector<uint32
   }
   HIP_OK(hipGetLastError());
   std::vector<double> tf(n);
-  for (size_t i = 0; i < n; ++i) {
-    const double ms = evs[i]->ms();
-    tf[i] = 4.0 * 32768.0 * iters * (static_cast<double>(blocks[i]) * 4) / (ms * 1e-3) / 1e12;
-  }
+  for (size_t i = 0; i < n; ++i) tf[i] = burn_tflops(blocks[i], iters, evs[i]->ms());
   return tf;
 }
 
@@ -834,7 +819,7 @@ std::vector<double> hbm_colocated(int dev, const std::vector<std::vector<uint32_
   HIP_OK(hipGetLastError());
   std::vector<double> gbs(k);
   for (size_t i = 0; i < k; ++i)
-    gbs[i] = 2.0 * static_cast<double>(n * sizeof(float4)) * iters_each[i] / (evs[i]->ms() * 1e-3) / 1e9;
+    gbs[i] = copy_gbs(n, iters_each[i], evs[i]->ms());
   return gbs;
 }
 
@@ -868,9 +853,8 @@ std::vector<double> mixed_colocated(int dev, const std::vector<uint32_t>& hbm_ma
     hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, sc.s, src.p, dst.p, n);
   HIP_OK(hipEventRecord(ec.b, sc.s));
   HIP_OK(hipGetLastError());
-  const double gbs = 2.0 * static_cast<double>(n * sizeof(float4)) * iters / (ec.ms() * 1e-3) / 1e9;
-  const double tf = 4.0 * 32768.0 * mfma_iters * (static_cast<double>(mfma_blocks) * 4) / (em.ms() * 1e-3) / 1e12;
-  return {gbs, tf};
+  const double gbs = copy_gbs(n, iters, ec.ms());
+  return {gbs, burn_tflops(mfma_blocks, mfma_iters, em.ms())};
 }
 
 struct PeerRate {
@@ -1031,15 +1015,32 @@ struct ExpectedFlip {
   uint32_t word = 0, mask = 0;
 };
 
+using SweepKernel = void (*)(const float*, uint32_t*, uint32_t, SweepInject, uint32_t, uint32_t, const uint32_t*);
+constexpr SweepKernel kSweepKernels[2][2] = {   // [kPaths][kFull]
+    {cu_sweep_kernel<false, false>, cu_sweep_kernel<false, true>},
+    {cu_sweep_kernel<true, false>, cu_sweep_kernel<true, true>}};
+
+bool sweep_block_fits(SweepKernel kernel, size_t dynamic_lds) {
+  int fit = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, kSweepBlock, dynamic_lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return fit >= 1;
+}
+
 // rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
 // hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
-// `paths` != 0 launches the cu_sweep_paths kernels instead (same grid, block and LDS), with
-// every path's expected tile uploaded once, and returns their 7-word records.
+// `paths` != 0 launches the kPaths instantiations instead (same grid, block and LDS), with
+// every path's expected tile uploaded once, and returns their 7-word records. `lds_bytes`
+// (test hook) takes the dynamic-LDS instantiation with that much LDS whatever the device allows.
 // The session holds the buffers, the stream and the kernel choice, made once; `run` launches
 // and reads back. cu_sweep is one session and one run, sweep_sensitivity a run per word.
 class SweepSession {
  public:
-  SweepSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t paths) : paths_(paths), stream_(mask) {
+  SweepSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t paths,
+               std::optional<size_t> lds_bytes = std::nullopt)
+      : paths_(paths), stream_(mask) {
     if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
     int cus = 0;
     if (mask.empty())
@@ -1049,26 +1050,23 @@ class SweepSession {
     if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep: the mask enables no CU");
     blocks_ = rounds * cus;
 
-    int fit = 0;
     if (paths & ~sp::kAllPaths) throw std::invalid_argument("cu_sweep_paths: unknown path bit");
-    if ((paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_full, kSweepBlock, 0)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_full, kSweepBlock, 0)) != hipSuccess) {
-      (void)hipGetLastError();
-      fit = 0;
-    }
-    full_ = fit >= 1;
-    if (!full_) {
-      hipDeviceProp_t p;
-      HIP_OK(hipGetDeviceProperties(&p, dev));
-      n_ = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
-      fit = 0;
-      if (n_ < (paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u) ||
-          (paths ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_paths_part, kSweepBlock, n_ * 4u)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, cu_sweep_part, kSweepBlock, n_ * 4u)) != hipSuccess ||
-          fit < 1) {
-        (void)hipGetLastError();
-        throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
+    const uint32_t n_min = paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u;   // staging | reduction
+    if (lds_bytes && (*lds_bytes % 16 != 0 || *lds_bytes > 65536 || *lds_bytes < n_min * 4u))
+      throw std::invalid_argument("cu_sweep: lds_bytes is a multiple of 16, " + std::to_string(n_min * 4u) + "..65536");
+    kernel_ = kSweepKernels[paths != 0][1];
+    if (lds_bytes || !sweep_block_fits(kernel_, 0)) {
+      kernel_ = kSweepKernels[paths != 0][0];
+      if (lds_bytes) {
+        n_ = static_cast<uint32_t>(*lds_bytes / 4);
+      } else {
+        hipDeviceProp_t p;
+        HIP_OK(hipGetDeviceProperties(&p, dev));
+        n_ = static_cast<uint32_t>(std::min<size_t>(p.sharedMemPerBlock, kLdsDwordsFull * 4u) / 4);
       }
+      dynamic_lds_ = n_ * 4u;
+      if (n_ < n_min || !sweep_block_fits(kernel_, dynamic_lds_))
+        throw std::runtime_error("cu_sweep: no sweep workgroup fits a CU of this device");
     }
 
     std::vector<int32_t> tile(32 * 32);
@@ -1078,10 +1076,11 @@ class SweepSession {
     HIP_OK(hipMemcpy(expected_->p, expected_host_.data(), expected_host_.size() * sizeof(float), hipMemcpyHostToDevice));
     record_words_ = paths ? sp::kPathRecordWords : st::kSweepRecordWords;
     out_.reset(new DevBuf<uint32_t>(static_cast<size_t>(blocks_) * record_words_));
-    tiles_.reset(new DevBuf<uint32_t>(paths ? path_tiles().size() : 1));
-    if (paths)
+    if (paths) {
+      tiles_.reset(new DevBuf<uint32_t>(path_tiles().size()));
       HIP_OK(hipMemcpy(tiles_->p, path_tiles().data(), path_tiles().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    launch(1, 0u, SweepInject{-1, -1, kInjectNone, 0});   // loads the code object outside the timed span
+    }
+    launch(1, 0u, SweepInject{});   // loads the code object outside the timed span
   }
 
   // Puts the device's expected data back as the host computed it, then XORs `f`'s word. The
@@ -1115,7 +1114,7 @@ class SweepSession {
     res.words.resize(words);
     HIP_OK(hipMemcpy(res.words.data(), out_->p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < blocks_; ++b)
-      if (!(paths_ ? sp::decode_path_record(res.words.data(), b).base : st::decode_record(res.words.data(), b)).written())
+      if (!st::decode_record(res.words.data(), b, record_words_).written())
         throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
     return res;
   }
@@ -1135,17 +1134,8 @@ class SweepSession {
   }
 
   void launch(int blocks, uint32_t seed, SweepInject j) {
-    if (paths_ && full_)
-      hipLaunchKernelGGL(cu_sweep_paths_full, dim3(blocks), dim3(kSweepBlock), 0, stream_.s, expected_->p, out_->p, seed, j,
-                         paths_, tiles_->p);
-    else if (paths_)
-      hipLaunchKernelGGL(cu_sweep_paths_part, dim3(blocks), dim3(kSweepBlock), n_ * 4u, stream_.s, expected_->p, out_->p,
-                         seed, j, n_, paths_, tiles_->p);
-    else if (full_)
-      hipLaunchKernelGGL(cu_sweep_full, dim3(blocks), dim3(kSweepBlock), 0, stream_.s, expected_->p, out_->p, seed, j);
-    else
-      hipLaunchKernelGGL(cu_sweep_part, dim3(blocks), dim3(kSweepBlock), n_ * 4u, stream_.s, expected_->p, out_->p, seed,
-                         j, n_);
+    hipLaunchKernelGGL(kernel_, dim3(blocks), dim3(kSweepBlock), dynamic_lds_, stream_.s, expected_->p, out_->p, seed, j,
+                       n_, paths_, tiles_ ? tiles_->p : nullptr);
     HIP_OK(hipGetLastError());
   }
 
@@ -1153,18 +1143,18 @@ class SweepSession {
   Stream stream_;
   Events ev_;
   int blocks_ = 0, record_words_ = st::kSweepRecordWords;
-  uint32_t n_ = kLdsDwordsFull;
-  bool full_ = false;
+  SweepKernel kernel_ = nullptr;
+  uint32_t n_ = kLdsDwordsFull, dynamic_lds_ = 0;   // dwords the LDS test covers; bytes of them the launch asks for
   ExpectedFlip flip_;
   std::vector<float> expected_host_;
   std::unique_ptr<DevBuf<float>> expected_;
-  std::unique_ptr<DevBuf<uint32_t>> out_, tiles_;
+  std::unique_ptr<DevBuf<uint32_t>> out_, tiles_;   // tiles_: the path sweep only
 };
 
 SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj,
-                     uint32_t paths = 0, ExpectedFlip flip = {}) {
+                     uint32_t paths, ExpectedFlip flip, std::optional<size_t> lds_bytes) {
   HIP_OK(hipSetDevice(dev));
-  SweepSession session(dev, mask, rounds, paths);
+  SweepSession session(dev, mask, rounds, paths, lds_bytes);
   session.set_flip(flip);
   return session.run(seed, inj);
 }
@@ -1189,18 +1179,12 @@ Sensitivity sweep_sensitivity(int dev, const std::vector<uint32_t>& mask, int ro
   const Clock::time_point t0 = Clock::now();
   for (const auto& f : flips) {
     session.set_flip(ExpectedFlip{tile, f.first, f.second});
-    const SweepResult r = session.run(seed, SweepInject{-1, -1, kInjectNone, 0});
+    const SweepResult r = session.run(seed, SweepInject{});
     out.records = r.blocks;
     uint32_t a[4] = {~0u, ~0u, ~0u, ~0u}, o[4] = {0, 0, 0, 0};
     for (int b = 0; b < r.blocks; ++b) {
-      uint32_t v[4] = {0, 0, 0, 0};
-      if (paths) {
-        const sp::PathRecord rec = sp::decode_path_record(r.words.data(), b);
-        v[0] = rec.base.fail, v[1] = rec.base.lds_bad, v[2] = rec.path_fail, v[3] = rec.path_waves;
-      } else {
-        const st::SweepRecord rec = st::decode_record(r.words.data(), b);
-        v[0] = rec.fail, v[1] = rec.lds_bad;
-      }
+      const st::SweepRecord rec = st::decode_record(r.words.data(), b, r.record_words);
+      const uint32_t v[4] = {rec.fail, rec.lds_bad, rec.path_fail, rec.path_waves};
       for (int i = 0; i < 4; ++i) a[i] &= v[i], o[i] |= v[i];
     }
     out.fields.insert(out.fields.end(), a, a + 4);
@@ -1310,23 +1294,25 @@ int path_index(const std::string& name) {
   throw std::invalid_argument("unknown matrix path '" + name + "'");
 }
 
+using TileKernel = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*);
+
+// matrix_tile_kernel<P, opsel / 4, opsel % 4> for every opsel of the sequence: the byte selects
+// are immediates of the instruction. The unscaled paths have the one instantiation <P, 0, 0>.
+template <int P, int... I>
+TileKernel opsel_kernel(std::integer_sequence<int, I...>, int opsel) {
+  static constexpr TileKernel table[] = {matrix_tile_kernel<P, I / 4, I % 4>...};
+  return table[sizeof...(I) == 1 ? 0 : opsel];
+}
+
 template <int P>
-void launch_tile(int opsel, const uint32_t* A, const uint32_t* B, const uint32_t* SA, const uint32_t* SB, uint32_t* C) {
-#define NANOGPU_TILE_CASE(I)                                                                                  \
-  case I:                                                                                                     \
-    hipLaunchKernelGGL((matrix_tile_kernel<P, (I) / 4, (I) % 4>), dim3(1), dim3(64), 0, 0, A, B, SA, SB, C); \
-    break;
-  if constexpr (sp::path_scaled(P)) {
-    switch (opsel) {   // the byte selects are immediates of the instruction
-      NANOGPU_TILE_CASE(0) NANOGPU_TILE_CASE(1) NANOGPU_TILE_CASE(2) NANOGPU_TILE_CASE(3)
-      NANOGPU_TILE_CASE(4) NANOGPU_TILE_CASE(5) NANOGPU_TILE_CASE(6) NANOGPU_TILE_CASE(7)
-      NANOGPU_TILE_CASE(8) NANOGPU_TILE_CASE(9) NANOGPU_TILE_CASE(10) NANOGPU_TILE_CASE(11)
-      NANOGPU_TILE_CASE(12) NANOGPU_TILE_CASE(13) NANOGPU_TILE_CASE(14) NANOGPU_TILE_CASE(15)
-    }
-  } else {
-    hipLaunchKernelGGL((matrix_tile_kernel<P, 0, 0>), dim3(1), dim3(64), 0, 0, A, B, SA, SB, C);
-  }
-#undef NANOGPU_TILE_CASE
+TileKernel path_kernel(int opsel) {
+  return opsel_kernel<P>(std::make_integer_sequence<int, sp::path_scaled(P) ? 16 : 1>{}, opsel);
+}
+
+template <int... P>
+TileKernel tile_kernel(std::integer_sequence<int, P...>, int p, int opsel) {
+  static constexpr TileKernel (*table[])(int) = {path_kernel<P>...};
+  return table[p](opsel);
 }
 
 // One instruction of path `p` on the caller's codes: a_codes is A[row][k] (dim x K, row-major),
@@ -1336,6 +1322,7 @@ void launch_tile(int opsel, const uint32_t* A, const uint32_t* B, const uint32_t
 std::vector<uint32_t> matrix_tile(int p, const std::vector<uint64_t>& a_codes, const std::vector<uint64_t>& b_codes,
                                   const std::vector<uint32_t>& scale_a, const std::vector<uint32_t>& scale_b,
                                   int opsel_a, int opsel_b) {
+  if (p < 0 || p >= sp::kNumPaths) throw std::invalid_argument("matrix_tile: unknown path");
   const int dim = sp::path_dim(p), K = sp::path_k(p), cb = sp::path_code_bits(p), rowdw = sp::path_row_dwords(p);
   const size_t n = static_cast<size_t>(dim) * K;
   if (a_codes.size() != n || b_codes.size() != n)
@@ -1375,51 +1362,35 @@ std::vector<uint32_t> matrix_tile(int p, const std::vector<uint64_t>& a_codes, c
   HIP_OK(hipMemcpy(dsa.p, SA.data(), SA.size() * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(dsb.p, SB.data(), SB.size() * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemset(dc.p, 0, sp::kTileWords * 4));
-  const int opsel = opsel_a * 4 + opsel_b;
-  switch (p) {
-    case sp::kF16: launch_tile<sp::kF16>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kFp8: launch_tile<sp::kFp8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kBf8: launch_tile<sp::kBf8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kI8: launch_tile<sp::kI8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kMxFp8: launch_tile<sp::kMxFp8>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kMxFp6: launch_tile<sp::kMxFp6>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kMxFp4: launch_tile<sp::kMxFp4>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kF32: launch_tile<sp::kF32>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    case sp::kF64: launch_tile<sp::kF64>(opsel, da.p, db.p, dsa.p, dsb.p, dc.p); break;
-    default: throw std::invalid_argument("matrix_tile: unknown path");
-  }
+  hipLaunchKernelGGL(tile_kernel(AllPaths{}, p, opsel_a * 4 + opsel_b), dim3(1), dim3(64), 0, 0, da.p, db.p, dsa.p, dsb.p,
+                     dc.p);
   HIP_OK(hipGetLastError());
   std::vector<uint32_t> c(sp::path_tile_words(p));
   HIP_OK(hipMemcpy(c.data(), dc.p, c.size() * 4, hipMemcpyDeviceToHost));
   return c;
 }
 
-SweepInject parse_path_inject(const py::object& inject) {
-  SweepInject inj{-1, -1, kInjectNone, 0};
+// inject of cu_sweep: (xcc, cu_key, 'mfma' | 'lds'[, lds dword]); of cu_sweep_paths: (xcc, cu_key, path name).
+SweepInject parse_inject(const py::object& inject, bool paths) {
+  SweepInject inj;
   if (inject.is_none()) return inj;
   const py::tuple t = inject.cast<py::tuple>();
-  if (t.size() != 3) throw std::invalid_argument("cu_sweep_paths: inject = (xcc, cu_key, path name)");
-  inj.xcc = t[0].cast<int>();
-  inj.cu_key = t[1].cast<int>();
-  inj.kind = kInjectPath;
-  inj.lds_off = static_cast<uint32_t>(path_index(t[2].cast<std::string>()));
-  return inj;
-}
-
-SweepInject parse_inject(const py::object& inject) {
-  SweepInject inj{-1, -1, kInjectNone, 0};
-  if (inject.is_none()) return inj;
-  const py::tuple t = inject.cast<py::tuple>();
-  if (t.size() < 3 || t.size() > 4) throw std::invalid_argument("cu_sweep: inject = (xcc, cu_key, kind[, lds_dword])");
+  if (paths ? t.size() != 3 : t.size() < 3 || t.size() > 4)
+    throw std::invalid_argument(paths ? "cu_sweep_paths: inject = (xcc, cu_key, path name)"
+                                      : "cu_sweep: inject = (xcc, cu_key, kind[, lds_dword])");
   inj.xcc = t[0].cast<int>();
   inj.cu_key = t[1].cast<int>();
   const std::string kind = t[2].cast<std::string>();
-  if (kind == "mfma")
+  if (paths) {
+    inj.kind = kInjectPath;
+    inj.path = path_index(kind);
+  } else if (kind == "mfma") {
     inj.kind = kInjectMfma;
-  else if (kind == "lds")
+  } else if (kind == "lds") {
     inj.kind = kInjectLds;
-  else
+  } else {
     throw std::invalid_argument("cu_sweep: inject kind is 'mfma' or 'lds'");
+  }
   if (t.size() == 4) inj.lds_off = t[3].cast<uint32_t>();
   return inj;
 }
@@ -1439,6 +1410,48 @@ ExpectedFlip parse_flip(const py::object& corrupt, bool named) {
   f.word = t[named ? 1 : 0].cast<uint32_t>();
   f.mask = t[named ? 2 : 1].cast<uint32_t>();
   return f;
+}
+
+uint32_t path_bits(const std::vector<std::string>& names) {
+  uint32_t bits = 0;
+  for (const std::string& name : names) bits |= 1u << path_index(name);
+  return bits;
+}
+
+// cu_sweep (`paths` null: 5-field records) and cu_sweep_paths (7 fields, and the keys `paths` / `checked`).
+py::dict sweep_binding(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed,
+                       const std::vector<std::string>* paths, const py::object& inject, const py::object& corrupt_expected,
+                       std::optional<size_t> lds_bytes) {
+  const uint32_t bits = paths ? path_bits(*paths) : 0u;
+  if (paths && !bits) throw std::invalid_argument("cu_sweep_paths: no path selected");
+  const SweepInject inj = parse_inject(inject, paths != nullptr);
+  const ExpectedFlip flip = parse_flip(corrupt_expected, paths != nullptr);
+  SweepResult r;
+  {
+    py::gil_scoped_release nogil;
+    r = cu_sweep(dev, mask, rounds, seed, inj, bits, flip, lds_bytes);
+  }
+  py::list recs;
+  for (int b = 0; b < r.blocks; ++b) {
+    const st::SweepRecord rec = st::decode_record(r.words.data(), b, r.record_words);
+    const py::tuple base = py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds,
+                                          rec.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.lds_bad));
+    recs.append(paths ? py::tuple(base + py::make_tuple(rec.path_fail, rec.path_waves)) : base);
+  }
+  py::dict d;
+  d["records"] = recs;
+  if (paths) {
+    py::list names, checked;
+    for (int p = 0; p < sp::kNumPaths; ++p) {
+      names.append(sp::path_name(p));
+      if (bits >> p & 1u) checked.append(sp::path_name(p));
+    }
+    d["paths"] = names;
+    d["checked"] = checked;
+  }
+  d["lds_bytes"] = r.lds_bytes;
+  d["ms"] = r.ms;
+  return d;
 }
 
 }  // namespace
@@ -1514,33 +1527,20 @@ PYBIND11_MODULE(_probe, m) {
   m.def(
       "cu_sweep",
       [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const py::object& inject,
-         const py::object& corrupt_expected) {
-        const SweepInject inj = parse_inject(inject);
-        const ExpectedFlip flip = parse_flip(corrupt_expected, false);
-        SweepResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = cu_sweep(dev, mask, rounds, seed, inj, 0, flip);
-        }
-        py::list recs;
-        for (int b = 0; b < r.blocks; ++b) {
-          const st::SweepRecord rec = st::decode_record(r.words.data(), b);
-          recs.append(py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds,
-                                     rec.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.lds_bad)));
-        }
-        py::dict d;
-        d["records"] = recs;
-        d["lds_bytes"] = r.lds_bytes;
-        d["ms"] = r.ms;
-        return d;
+         const py::object& corrupt_expected, std::optional<size_t> lds_bytes) {
+        return sweep_binding(dev, mask, rounds, seed, nullptr, inject, corrupt_expected, lds_bytes);
       },
       py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
       py::arg("seed") = 0x5eed5eedu, py::arg("inject") = py::none(), py::arg("corrupt_expected") = py::none(),
+      py::arg("lds_bytes") = py::none(),
       "Deep CU check on a CU-masked stream: rounds x CUs workgroups, each holding a CU's whole LDS, run an "
       "exact bf16 MFMA chain on all 4 waves and a pattern test of the LDS. Records are (xcc, hw_id, fail bits, "
       "SIMD ids seen, first bad LDS dword or -1). inject = (xcc, cu_key, 'mfma' | 'lds'[, lds dword]) flips one "
       "bit of that CU's own data (tests). Test hook: corrupt_expected = (word, xor) XORs word 0..1023 of the host's "
-      "expected bf16 tile in the upload, so every wave of every visit must report the MFMA check failed.");
+      "expected bf16 tile in the upload, so every wave of every visit must report the MFMA check failed. Test hook: "
+      "lds_bytes (a multiple of 16, 16..65536) runs the dynamic-LDS kernel with that much LDS instead of the one a "
+      "device without room for a whole-LDS block would get; several such workgroups share a CU, so a visit of "
+      "every CU is not promised in this mode.");
   m.def(
       "matrix_tile",
       [](const std::string& path, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b,
@@ -1574,52 +1574,24 @@ PYBIND11_MODULE(_probe, m) {
   m.def(
       "cu_sweep_paths",
       [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& paths,
-         const py::object& inject, const py::object& corrupt_expected) {
-        uint32_t bits = 0;
-        for (const std::string& name : paths) bits |= 1u << path_index(name);
-        if (!bits) throw std::invalid_argument("cu_sweep_paths: no path selected");
-        const SweepInject inj = parse_path_inject(inject);
-        const ExpectedFlip flip = parse_flip(corrupt_expected, true);
-        SweepResult r;
-        {
-          py::gil_scoped_release nogil;
-          r = cu_sweep(dev, mask, rounds, seed, inj, bits, flip);
-        }
-        py::list recs;
-        for (int b = 0; b < r.blocks; ++b) {
-          const sp::PathRecord rec = sp::decode_path_record(r.words.data(), b);
-          recs.append(py::make_tuple(rec.base.xcc, rec.base.hw_id, rec.base.fail, rec.base.simds,
-                                     rec.base.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.base.lds_bad),
-                                     rec.path_fail, rec.path_waves));
-        }
-        py::list names, checked;
-        for (int p = 0; p < sp::kNumPaths; ++p) {
-          names.append(sp::path_name(p));
-          if (bits >> p & 1u) checked.append(sp::path_name(p));
-        }
-        py::dict d;
-        d["records"] = recs;
-        d["paths"] = names;
-        d["checked"] = checked;
-        d["lds_bytes"] = r.lds_bytes;
-        d["ms"] = r.ms;
-        return d;
+         const py::object& inject, const py::object& corrupt_expected, std::optional<size_t> lds_bytes) {
+        return sweep_binding(dev, mask, rounds, seed, &paths, inject, corrupt_expected, lds_bytes);
       },
       py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
       py::arg("seed") = 0x5eed5eedu, py::arg("paths") = std::vector<std::string>{}, py::arg("inject") = py::none(),
-      py::arg("corrupt_expected") = py::none(),
+      py::arg("corrupt_expected") = py::none(), py::arg("lds_bytes") = py::none(),
       "cu_sweep whose visits also run, on all 4 waves, an exact chain of 8 MFMA instructions of every path in "
       "`paths` and compare every accumulator bit with the host's tile. Records are cu_sweep's 5 fields plus "
       "(failed-path bits, waves that saw a path fail); `paths` in the result names the bits in order, `checked` "
       "the paths that ran. inject = (xcc, cu_key, path name) flips one accumulator bit of that path on that CU (tests). "
       "Test hook: corrupt_expected = ('bf16' | path name, word, xor) XORs one word of that expected tile (1024 "
-      "words, f64 512) in this call's upload, never in the host's cached tiles; the path must be selected.");
+      "words, f64 512) in this call's upload, never in the host's cached tiles; the path must be selected. Test hook: "
+      "lds_bytes as in cu_sweep, 36864 (the nine staged tiles)..65536; a visit of every CU is not promised then.");
   m.def(
       "sweep_sensitivity",
       [](int dev, const std::string& tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
          const std::vector<std::string>& paths, const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
-        uint32_t bits = 0;
-        for (const std::string& name : paths) bits |= 1u << path_index(name);
+        const uint32_t bits = path_bits(paths);
         const int t = tile_index(tile);
         Sensitivity r;
         {

@@ -69,14 +69,16 @@ constexpr uint32_t kRecordUnwritten = 0xffffffffu;   // the host fills the recor
 NANOGPU_HD inline uint32_t hw_cu_key(uint32_t hw_id) { return (hw_id >> 8) & 0xffu; }
 NANOGPU_HD inline uint32_t hw_simd(uint32_t hw_id) { return (hw_id >> 4) & 3u; }
 
+// cu_sweep_paths appends two words (selftest_paths_host.h: kPathRecordWords); a 5-word record has them 0.
 struct SweepRecord {
-  uint32_t xcc, hw_id, fail, simds, lds_bad;
+  uint32_t xcc, hw_id, fail, simds, lds_bad, path_fail, path_waves;
   bool written() const { return !(xcc == kRecordUnwritten && hw_id == kRecordUnwritten && fail == kRecordUnwritten); }
 };
 
-inline SweepRecord decode_record(const uint32_t* words, size_t block) {
-  const uint32_t* w = words + block * kSweepRecordWords;
-  return SweepRecord{w[0], w[1], w[2], w[3], w[4]};
+inline SweepRecord decode_record(const uint32_t* words, size_t block, int record_words) {
+  const uint32_t* w = words + block * static_cast<size_t>(record_words);
+  const bool paths = record_words > kSweepRecordWords;
+  return SweepRecord{w[0], w[1], w[2], w[3], w[4], paths ? w[5] : 0u, paths ? w[6] : 0u};
 }
 
 // ---- mismatch slot ----------------------------------------------------------------------

@@ -417,17 +417,7 @@ inline uint32_t path_coverage(int p) {
 // Words 0..4 are cu_sweep's record, with the same meaning (the bf16 chain and the LDS test
 // still run). Word 5: bit p is set when path p's chain differed from its tile on any wave.
 // Word 6: bit w (0..3) is set when wave w saw any path differ.
-constexpr int kPathRecordWords = 7;
-
-struct PathRecord {
-  SweepRecord base;
-  uint32_t path_fail, path_waves;
-};
-
-inline PathRecord decode_path_record(const uint32_t* words, size_t block) {
-  const uint32_t* w = words + block * kPathRecordWords;
-  return PathRecord{SweepRecord{w[0], w[1], w[2], w[3], w[4]}, w[5], w[6]};
-}
+constexpr int kPathRecordWords = 7;   // decoded by decode_record(words, block, kPathRecordWords)
 
 }  // namespace paths
 }  // namespace selftest

@@ -59,8 +59,10 @@ int main() {
   // record decode
   const uint32_t words[10] = {3, 0x0000a5b0u, 0x12, 0xf, 40959, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu,
                               0xffffffffu};
-  const st::SweepRecord r0 = st::decode_record(words, 0), r1 = st::decode_record(words, 1);
+  const st::SweepRecord r0 = st::decode_record(words, 0, st::kSweepRecordWords),
+                        r1 = st::decode_record(words, 1, st::kSweepRecordWords);
   CHECK(r0.written() && !r1.written());
+  CHECK(r0.path_fail == 0 && r0.path_waves == 0);   // a 5-word record has no path words
   CHECK(r0.xcc == 3 && st::hw_cu_key(r0.hw_id) == 0xa5 && st::hw_simd(r0.hw_id) == 3);
   CHECK((r0.fail & st::kFailLds) && (r0.fail & 0xf) == 2 && r0.lds_bad == 40959);
 

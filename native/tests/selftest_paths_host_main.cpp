@@ -90,9 +90,13 @@ int main() {
   // record decode
   const uint32_t words[14] = {3, 0x0000a5b0u, 0, 0xf, 0xffffffffu, 0x41, 0x5, 0xffffffffu, 0xffffffffu, 0xffffffffu,
                               0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-  const sp::PathRecord r0 = sp::decode_path_record(words, 0), r1 = sp::decode_path_record(words, 1);
-  CHECK(r0.base.written() && !r1.base.written());
-  CHECK(r0.base.xcc == 3 && r0.path_fail == ((1u << sp::kF16) | (1u << sp::kMxFp4)) && r0.path_waves == 5);
+  namespace st = nanogpu::selftest;
+  const st::SweepRecord r0 = st::decode_record(words, 0, sp::kPathRecordWords),
+                        r1 = st::decode_record(words, 1, sp::kPathRecordWords);
+  CHECK(r0.written() && !r1.written());
+  CHECK(r0.xcc == 3 && r0.path_fail == ((1u << sp::kF16) | (1u << sp::kMxFp4)) && r0.path_waves == 5);
+  const st::SweepRecord r5 = st::decode_record(words, 0, st::kSweepRecordWords);   // the same words as a plain record
+  CHECK(r5.written() && r5.xcc == 3 && r5.path_fail == 0 && r5.path_waves == 0);
 
   if (failures) return 1;
   std::puts(json.c_str());
