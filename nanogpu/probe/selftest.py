@@ -706,7 +706,7 @@ def main(argv: list[str] | None = None) -> int:
                   + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
-                  f"verify {h['verify_gbs']:.0f} GB/s")
+                  f"verify {h['verify_gbs']:.0f} GB/s, {h.get('verify_launches', 1)} launch(es) a pass")
         if not rep.ok:
             print("  " + rep.describe_failure())
         for n in rep.notes:

@@ -48,6 +48,8 @@ namespace py = pybind11;
 
 namespace {
 
+namespace st = nanogpu::selftest;
+
 // ---------------------------------------------------------------------------- kernels
 
 // Streaming copy: each thread keeps kCopyUnroll 16-B loads in flight before its stores
@@ -74,8 +76,22 @@ __global__ __launch_bounds__(kCopyBlock) void hbm_copy(const float4* __restrict_
   }
 }
 
+static_assert(kCopyBlock == st::kLaunchThreads && kCopyBlock * kCopyUnroll == st::kBlockElements,
+              "launch_spans counts blocks of this shape");
+
+// HIP supports no launch of 2^32 work-items or more: with 256 threads a block, 2^24 blocks
+// (256 GiB of float4). Nobody measures a copy that large, so it is refused, before any allocation.
 inline unsigned copy_grid(size_t n) {
-  return static_cast<unsigned>((n + kCopyBlock * kCopyUnroll - 1) / (kCopyBlock * kCopyUnroll));
+  const uint64_t blocks = st::span_blocks(n);
+  if (blocks * st::kLaunchThreads >= st::kWorkItemLimit)
+    throw std::invalid_argument("hbm_copy: " + std::to_string(n) + " elements need 2^32 work-items or more in one launch");
+  return static_cast<unsigned>(blocks);
+}
+
+// mfma_burn's blocks of 256 threads, under the same limit.
+inline void check_burn_blocks(int blocks) {
+  if (blocks <= 0 || static_cast<uint64_t>(blocks) * 256 >= st::kWorkItemLimit)
+    throw std::invalid_argument("mfma_burn: block count in 1..2^24 - 1");
 }
 
 // One record per workgroup: {xcc_id, hw_id, block}. A bounded sleep keeps each workgroup
@@ -133,8 +149,6 @@ __global__ __launch_bounds__(64) void mfma_tile(const __bf16* __restrict__ A, co
 }
 
 // ---------------------------------------------------------------------------- deep self-test
-
-namespace st = nanogpu::selftest;
 
 constexpr int kSweepBlock = 256;               // 4 waves: one per SIMD's MFMA pipe
 constexpr uint32_t kLdsDwordsFull = 40960;     // 160 KiB: the whole LDS of a gfx950 CU
@@ -464,7 +478,9 @@ __global__ __launch_bounds__(kSweepBlock) void cu_sweep_kernel(const float* __re
 }
 
 // HBM pattern test in hbm_copy's shape (256 threads, 4 x 16 B per thread in flight,
-// non-temporal, one pass, scalar tail): hbm_fill only writes, hbm_verify only reads.
+// non-temporal, one pass, scalar tail): hbm_fill only writes, hbm_verify only reads. One launch
+// covers the n elements at dst / src, which are elements first.. of the buffer (st::launch_spans):
+// the pattern and the reported element are the buffer's, first + i.
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
 __device__ __forceinline__ u32x4 pattern4(uint64_t i, uint32_t seed, uint32_t pass) {
@@ -476,16 +492,16 @@ __device__ __forceinline__ u32x4 pattern4(uint64_t i, uint32_t seed, uint32_t pa
   return p;
 }
 
-__global__ __launch_bounds__(kCopyBlock) void hbm_fill(u32x4* __restrict__ dst, size_t n, uint32_t seed,
-                                                       uint32_t pass) {
+__global__ __launch_bounds__(kCopyBlock) void hbm_fill(u32x4* __restrict__ dst, size_t n, uint64_t first,
+                                                       uint32_t seed, uint32_t pass) {
   const size_t base = static_cast<size_t>(blockIdx.x) * (kCopyBlock * kCopyUnroll) + threadIdx.x;
   if (base + (kCopyUnroll - 1) * kCopyBlock < n) {
 #pragma unroll
     for (int u = 0; u < kCopyUnroll; ++u)
-      __builtin_nontemporal_store(pattern4(base + u * kCopyBlock, seed, pass), dst + base + u * kCopyBlock);
+      __builtin_nontemporal_store(pattern4(first + base + u * kCopyBlock, seed, pass), dst + base + u * kCopyBlock);
   } else {
     for (int u = 0; u < kCopyUnroll; ++u)
-      if (base + u * kCopyBlock < n) dst[base + u * kCopyBlock] = pattern4(base + u * kCopyBlock, seed, pass);
+      if (base + u * kCopyBlock < n) dst[base + u * kCopyBlock] = pattern4(first + base + u * kCopyBlock, seed, pass);
   }
 }
 
@@ -511,18 +527,18 @@ __device__ __forceinline__ void verify_one(uint64_t i, u32x4 got, uint32_t seed,
   m->pad = 0;
 }
 
-__global__ __launch_bounds__(kCopyBlock) void hbm_verify(const u32x4* __restrict__ src, size_t n, uint32_t seed,
-                                                         uint32_t pass, VerifyOut* __restrict__ o) {
+__global__ __launch_bounds__(kCopyBlock) void hbm_verify(const u32x4* __restrict__ src, size_t n, uint64_t first,
+                                                         uint32_t seed, uint32_t pass, VerifyOut* __restrict__ o) {
   const size_t base = static_cast<size_t>(blockIdx.x) * (kCopyBlock * kCopyUnroll) + threadIdx.x;
   if (base + (kCopyUnroll - 1) * kCopyBlock < n) {
     u32x4 v[kCopyUnroll];
 #pragma unroll
     for (int u = 0; u < kCopyUnroll; ++u) v[u] = __builtin_nontemporal_load(src + base + u * kCopyBlock);
 #pragma unroll
-    for (int u = 0; u < kCopyUnroll; ++u) verify_one(base + u * kCopyBlock, v[u], seed, pass, o);
+    for (int u = 0; u < kCopyUnroll; ++u) verify_one(first + base + u * kCopyBlock, v[u], seed, pass, o);
   } else {
     for (int u = 0; u < kCopyUnroll; ++u)
-      if (base + u * kCopyBlock < n) verify_one(base + u * kCopyBlock, src[base + u * kCopyBlock], seed, pass, o);
+      if (base + u * kCopyBlock < n) verify_one(first + base + u * kCopyBlock, src[base + u * kCopyBlock], seed, pass, o);
   }
 }
 
@@ -665,6 +681,7 @@ CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
   HIP_OK(hipSetDevice(dev));
   check_guard_bytes(guard_bytes);
   const size_t n4 = (n_floats + 3) / 4;
+  const dim3 grid(copy_grid(n4));
   std::vector<float> h(n4 * 4);
   for (size_t i = 0; i < h.size(); ++i) h[i] = static_cast<float>((i * 2654435761u) % 1000003u);
   DevBuf<float4> a(n4);
@@ -673,7 +690,7 @@ CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
   HIP_OK(hipMemcpy(a.p, h.data(), n4 * 16, hipMemcpyHostToDevice));
   if (guard_bytes) HIP_OK(hipMemset(b.p, kGuardByte, n4 * 16 + 2 * guard_bytes));
   HIP_OK(hipMemset(dst, 0, n4 * 16));
-  hipLaunchKernelGGL(hbm_copy, dim3(copy_grid(n4)), dim3(kCopyBlock), 0, 0, a.p, dst, n4);
+  hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, 0, a.p, dst, n4);
   HIP_OK(hipGetLastError());
   std::vector<float> out(n4 * 4);
   HIP_OK(hipMemcpy(out.data(), dst, n4 * 16, hipMemcpyDeviceToHost));
@@ -687,11 +704,11 @@ double hbm_bandwidth(int dev, size_t bytes, int iters) {
   HIP_OK(hipSetDevice(dev));
   const size_t n = bytes / sizeof(float4);
   if (n == 0 || iters <= 0) throw std::invalid_argument("hbm_bandwidth: bytes/iters must be positive");
+  const dim3 grid(copy_grid(n));
   DevBuf<float4> a(n), b(n);
   HIP_OK(hipMemset(a.p, 0, n * sizeof(float4)));
   Stream st({});
   Events ev;
-  const dim3 grid(copy_grid(n));
   hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);  // warm-up
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev.a, st.s));
@@ -721,6 +738,7 @@ py::list census(int dev, const std::vector<uint32_t>& mask, int blocks, int slee
 double mfma_ms(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
   HIP_OK(hipSetDevice(dev));
   if (blocks <= 0 || iters <= 0) throw std::invalid_argument("mfma_throughput: bad shape");
+  check_burn_blocks(blocks);
   DevBuf<float> out(static_cast<size_t>(blocks) * 256);
   Stream st(mask);
   Events ev;
@@ -761,8 +779,8 @@ std::vector<double> mfma_colocated(int dev, const std::vector<std::vector<uint32
   std::vector<std::unique_ptr<Stream>> streams;
   std::vector<std::unique_ptr<Events>> evs;
   std::vector<std::unique_ptr<DevBuf<float>>> outs;
+  for (int b : blocks) check_burn_blocks(b);
   for (size_t i = 0; i < n; ++i) {
-    if (blocks[i] <= 0) throw std::invalid_argument("mfma_colocated: bad block count");
     streams.emplace_back(new Stream(masks[i]));
     evs.emplace_back(new Events());
     outs.emplace_back(new DevBuf<float>(static_cast<size_t>(blocks[i]) * 256));
@@ -835,12 +853,13 @@ std::vector<double> mixed_colocated(int dev, const std::vector<uint32_t>& hbm_ma
   const size_t n = bytes / sizeof(float4);
   if (n == 0 || iters <= 0 || mfma_blocks <= 0 || mfma_iters <= 0)
     throw std::invalid_argument("mixed_colocated: bytes, iters and the burn shape must be positive");
+  const dim3 grid(copy_grid(n));
+  check_burn_blocks(mfma_blocks);
   Stream sc(hbm_mask), sm(mfma_mask);
   Events ec, em;
   DevBuf<float4> src(n), dst(n);
   DevBuf<float> out(static_cast<size_t>(mfma_blocks) * 256);
   HIP_OK(hipMemset(src.p, 0, n * sizeof(float4)));
-  const dim3 grid(copy_grid(n));
   hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, sc.s, src.p, dst.p, n);    // warm-up
   hipLaunchKernelGGL(mfma_burn, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, 8);
   HIP_OK(hipGetLastError());
@@ -896,6 +915,7 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
     throw std::invalid_argument("peer_bandwidth: need two distinct visible devices");
   const size_t n = bytes / sizeof(float4);
   if (n == 0 || iters <= 0) throw std::invalid_argument("peer_bandwidth: bytes/iters must be positive");
+  const dim3 grid(copy_grid(n));
   const Clock::time_point deadline =
       Clock::now() + std::chrono::microseconds(static_cast<int64_t>((deadline_s > 0 ? deadline_s : 30.0) * 1e6));
   PeerRate r{0.0, 0.0, false};
@@ -966,7 +986,6 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
       for (int i = 0; i < iters; ++i) HIP_OK(hipMemcpyPeerAsync(b, dst, a, src, n * sizeof(float4), st));
     }) / 1e9;
     if (r.peer_access) {
-      const dim3 grid(copy_grid(n));
       timed("pull warm-up", [&] {
         hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st, a, b, n);
         HIP_OK(hipGetLastError());
@@ -1200,15 +1219,26 @@ struct PatternResult {
   std::vector<st::Mismatch> first;
   double fill_gbs = 0.0, verify_gbs = 0.0;
   size_t guard_changed = 0;   // guard bytes overwritten (guard_bytes > 0 only)
+  size_t fill_launches = 0, verify_launches = 0;   // per pass
 };
+
+// Blocks a launch of hbm_fill / hbm_verify: 0 is the production bound, 1..kMaxLaunchBlocks a test's own.
+uint64_t launch_blocks_arg(long long v) {
+  if (v < 0 || static_cast<uint64_t>(v) > st::kMaxLaunchBlocks)
+    throw std::invalid_argument("hbm_pattern_check: launch blocks in 0.." + std::to_string(st::kMaxLaunchBlocks) +
+                                " (0: that many)");
+  return v == 0 ? st::kMaxLaunchBlocks : static_cast<uint64_t>(v);
+}
 
 // Fill `bytes` of fresh device memory with the address-derived pattern and verify it, `passes`
 // times (odd passes: the complement). `corrupt` = (byte offset, xor byte) pairs the host applies
 // between a pass's fill and its verify; `verify_seed` < 0 verifies with `seed`. `guard_bytes`
-// (tests) puts the buffer between two guard regions, see kGuardByte.
+// (tests) puts the buffer between two guard regions, see kGuardByte. A pass is one launch after
+// another on one stream (st::launch_spans), each below 2^32 work-items, under one pair of events;
+// `fill_launch_blocks` / `verify_launch_blocks` (tests) move the seams between them, separately.
 PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes,
                                 const std::vector<std::pair<uint64_t, uint32_t>>& corrupt, int64_t verify_seed,
-                                size_t guard_bytes) {
+                                size_t guard_bytes, long long fill_launch_blocks, long long verify_launch_blocks) {
   HIP_OK(hipSetDevice(dev));
   check_guard_bytes(guard_bytes);
   if (bytes == 0 || bytes % 16 != 0) throw std::invalid_argument("hbm_pattern_check: bytes must be a positive multiple of 16");
@@ -1217,8 +1247,8 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
     if (c.first >= bytes + guard_bytes || c.second > 0xff)   // with a guard, the guard behind the buffer too
       throw std::invalid_argument("hbm_pattern_check: corrupt = (offset < bytes, xor byte)");
   const size_t n = bytes / 16;
-  if ((n + kCopyBlock * kCopyUnroll - 1) / (kCopyBlock * kCopyUnroll) > 0x7fffffffull)   // gridDim.x
-    throw std::invalid_argument("hbm_pattern_check: too large for one launch");
+  const auto fill_spans = st::launch_spans(n, launch_blocks_arg(fill_launch_blocks));
+  const auto verify_spans = st::launch_spans(n, launch_blocks_arg(verify_launch_blocks));
   const uint32_t vseed = verify_seed < 0 ? seed : static_cast<uint32_t>(verify_seed);
 
   struct Buf {   // an allocation that does not fit is the caller's to shrink, not a device fault
@@ -1246,15 +1276,17 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   Events ev;
   HIP_OK(hipMemsetAsync(vo.p, 0, sizeof(VerifyOut), stream.s));
   // n = 0 touches no memory: loads both kernels outside the timed spans
-  hipLaunchKernelGGL(hbm_fill, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), seed, 0u);
-  hipLaunchKernelGGL(hbm_verify, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), seed, 0u, vo.p);
+  hipLaunchKernelGGL(hbm_fill, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), uint64_t(0), seed, 0u);
+  hipLaunchKernelGGL(hbm_verify, dim3(1), dim3(kCopyBlock), 0, stream.s, data, size_t(0), uint64_t(0), seed, 0u, vo.p);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(stream.s));
-  const dim3 grid(copy_grid(n));
+  auto grid_of = [](uint64_t elements) { return dim3(static_cast<unsigned>(st::span_blocks(elements))); };
   double fill_ms = 0.0, verify_ms = 0.0;
   for (int pass = 0; pass < passes; ++pass) {
     HIP_OK(hipEventRecord(ev.a, stream.s));
-    hipLaunchKernelGGL(hbm_fill, grid, dim3(kCopyBlock), 0, stream.s, data, n, seed, static_cast<uint32_t>(pass));
+    for (const auto& span : fill_spans)
+      hipLaunchKernelGGL(hbm_fill, grid_of(span.second), dim3(kCopyBlock), 0, stream.s, data + span.first,
+                         static_cast<size_t>(span.second), span.first, seed, static_cast<uint32_t>(pass));
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ev.b, stream.s));
     fill_ms += ev.ms();
@@ -1266,7 +1298,9 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
       HIP_OK(hipMemcpy(at, &byte, 1, hipMemcpyHostToDevice));
     }
     HIP_OK(hipEventRecord(ev.a, stream.s));
-    hipLaunchKernelGGL(hbm_verify, grid, dim3(kCopyBlock), 0, stream.s, data, n, vseed, static_cast<uint32_t>(pass), vo.p);
+    for (const auto& span : verify_spans)
+      hipLaunchKernelGGL(hbm_verify, grid_of(span.second), dim3(kCopyBlock), 0, stream.s, data + span.first,
+                         static_cast<size_t>(span.second), span.first, vseed, static_cast<uint32_t>(pass), vo.p);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(ev.b, stream.s));
     verify_ms += ev.ms();
@@ -1285,6 +1319,8 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   res.fill_gbs = moved / (fill_ms * 1e-3) / 1e9;
   res.verify_gbs = moved / (verify_ms * 1e-3) / 1e9;
   res.guard_changed = guard_bytes_changed(whole.p, guard_bytes, bytes);
+  res.fill_launches = fill_spans.size();
+  res.verify_launches = verify_spans.size();
   return res;
 }
 
@@ -1619,12 +1655,14 @@ PYBIND11_MODULE(_probe, m) {
   m.def(
       "hbm_pattern_check",
       [](int dev, size_t bytes, uint32_t seed, int passes, const std::vector<std::pair<uint64_t, uint32_t>>& corrupt,
-         const py::object& verify_seed, size_t guard_bytes) {
+         const py::object& verify_seed, size_t guard_bytes, long long fill_launch_blocks,
+         long long verify_launch_blocks) {
         const int64_t vseed = verify_seed.is_none() ? int64_t(-1) : int64_t(verify_seed.cast<uint32_t>());
         PatternResult r;
         {
           py::gil_scoped_release nogil;
-          r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed, guard_bytes);
+          r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed, guard_bytes, fill_launch_blocks,
+                                verify_launch_blocks);
         }
         py::list first;
         for (const st::Mismatch& mm : r.first)
@@ -1635,18 +1673,24 @@ PYBIND11_MODULE(_probe, m) {
         d["first"] = first;
         d["fill_gbs"] = r.fill_gbs;
         d["verify_gbs"] = r.verify_gbs;
+        d["fill_launches"] = r.fill_launches;
+        d["verify_launches"] = r.verify_launches;
         if (guard_bytes) d["guard_ok"] = r.guard_changed == 0;
         return d;
       },
       py::arg("device") = 0, py::arg("bytes") = size_t(256) << 20, py::arg("seed") = 0x5eed5eedu,
       py::arg("passes") = 2, py::arg("corrupt") = std::vector<std::pair<uint64_t, uint32_t>>{},
-      py::arg("verify_seed") = py::none(), py::arg("guard_bytes") = size_t(0),
+      py::arg("verify_seed") = py::none(), py::arg("guard_bytes") = size_t(0), py::arg("fill_launch_blocks") = 0LL,
+      py::arg("verify_launch_blocks") = 0LL,
       "Fills `bytes` of device memory with an address-derived pattern and verifies it (odd passes: the "
       "complement). errors counts mismatching 16-byte elements over all passes; first = up to 16 of "
       "(byte offset of the first differing byte, expected word, got word). corrupt = [(byte offset, xor byte)] "
       "is applied by the host between fill and verify. Test hook: guard_bytes > 0 (a multiple of 16) puts the "
       "buffer between two guard regions of that size and adds guard_ok, false when a guard byte changed: a kernel "
-      "wrote outside the buffer, or `corrupt` named an offset in the guard behind it (bytes <= offset < bytes + guard_bytes). Raises MemoryError when the buffer cannot be allocated.");
+      "wrote outside the buffer, or `corrupt` named an offset in the guard behind it (bytes <= offset < bytes + guard_bytes). A pass is one launch after another of at most 2^22 blocks (64 GiB), "
+      "each below the 2^32 work-items HIP supports; fill_launches / verify_launches count them per pass. Test hook: "
+      "fill_launch_blocks / verify_launch_blocks = blocks of 1,024 elements a launch of the fill / of the verify "
+      "(0: 2^22; 1..2^22; anything else raises ValueError). Raises MemoryError when the buffer cannot be allocated.");
   m.def(
       "mem_info",
       [](int dev) {

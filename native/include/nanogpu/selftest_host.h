@@ -6,6 +6,8 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define NANOGPU_HD __host__ __device__
@@ -39,6 +41,31 @@ NANOGPU_HD inline uint32_t pattern_word(uint64_t i, uint32_t k, uint32_t seed, u
   const uint32_t v = mix32(static_cast<uint32_t>(w) ^ seed) ^ (static_cast<uint32_t>(w >> 32) * kHiMul);
   return (pass & 1u) ? ~v : v;
 }
+
+// ---- launch spans ----------------------------------------------------------------------
+// hbm_fill and hbm_verify run 256 threads a block and 4 elements a thread. HIP supports no
+// launch of 2^32 work-items or more, which a single launch over a buffer of 256 GiB would be,
+// so a buffer is covered by one launch after another of at most kMaxLaunchBlocks blocks:
+// 64 GiB a launch, the largest single launch measured (profiles/gpu_calibration.md).
+constexpr uint64_t kLaunchThreads = 256;
+constexpr uint64_t kBlockElements = 4 * kLaunchThreads;
+constexpr uint64_t kWorkItemLimit = uint64_t(1) << 32;
+constexpr uint64_t kMaxLaunchBlocks = uint64_t(1) << 22;
+static_assert(kMaxLaunchBlocks * kLaunchThreads < kWorkItemLimit, "a launch stays below 2^32 work-items");
+
+// (first element, elements) of the launches that tile [0, n_elements) in order: every span is
+// max_blocks whole blocks, the last one what is left (its last block may be partial).
+// max_blocks in 1..kMaxLaunchBlocks is the caller's to check.
+inline std::vector<std::pair<uint64_t, uint64_t>> launch_spans(uint64_t n_elements, uint64_t max_blocks) {
+  std::vector<std::pair<uint64_t, uint64_t>> spans;
+  const uint64_t step = max_blocks * kBlockElements;
+  spans.reserve(static_cast<size_t>((n_elements + step - 1) / step));
+  for (uint64_t first = 0; first < n_elements; first += step)
+    spans.emplace_back(first, n_elements - first < step ? n_elements - first : step);
+  return spans;
+}
+
+inline uint64_t span_blocks(uint64_t elements) { return (elements + kBlockElements - 1) / kBlockElements; }
 
 // ---- MFMA chain -------------------------------------------------------------------------
 // C = sum over steps s of A_s[32x16] * B_s[16x32], small integers rotated per step:

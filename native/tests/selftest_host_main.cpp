@@ -36,6 +36,34 @@ int main() {
   // words 2^32 apart (16 GiB) differ: the high half of the word index is in the value
   CHECK(st::pattern_word(5, 1, 3, 0) != st::pattern_word(5 + (1ull << 30), 1, 3, 0));
 
+  // launch spans: contiguous from 0, whole blocks but the last, within the bound, below 2^32 work-items
+  const uint64_t ns[] = {1, 1023, 1024, 1025, (1ull << 34) - 1, 1ull << 34, (1ull << 34) + 1, 19ull << 30};   // 19 * 2^30 elements: 304 GiB
+  for (uint64_t max_blocks : {uint64_t(1), uint64_t(3), uint64_t(65535), st::kMaxLaunchBlocks}) {
+    CHECK(st::launch_spans(0, max_blocks).empty());
+    for (uint64_t n : ns) {
+      const auto spans = st::launch_spans(n, max_blocks);
+      CHECK(!spans.empty());
+      uint64_t next = 0;
+      for (size_t j = 0; j < spans.size(); ++j) {
+        const uint64_t first = spans[j].first, elements = spans[j].second;
+        CHECK(first == next);
+        CHECK(elements > 0 && elements <= max_blocks * st::kBlockElements);
+        CHECK(first % st::kBlockElements == 0);
+        if (j + 1 < spans.size()) CHECK(elements == max_blocks * st::kBlockElements);   // only the last one is short
+        CHECK(st::span_blocks(elements) <= max_blocks);
+        CHECK(st::span_blocks(elements) * st::kLaunchThreads < st::kWorkItemLimit);
+        CHECK(st::span_blocks(elements) * st::kBlockElements >= elements);              // the grid covers the span
+        next = first + elements;
+      }
+      CHECK(next == n);
+      CHECK(spans.size() == (n + max_blocks * st::kBlockElements - 1) / (max_blocks * st::kBlockElements));
+    }
+  }
+  CHECK(st::launch_spans(7 * 1024 + 5, 3) ==
+        (std::vector<std::pair<uint64_t, uint64_t>>{{0, 3072}, {3072, 3072}, {6144, 1029}}));
+  CHECK(st::launch_spans(19ull << 30, st::kMaxLaunchBlocks).size() == 5);   // 304 GiB: 4 launches of 64 GiB and one of 48
+  CHECK(st::span_blocks(1) == 1 && st::span_blocks(1024) == 1 && st::span_blocks(1025) == 2);
+
   // expected tile: operand ranges, the exactness bound, and one entry by hand
   for (int s = 0; s < st::kSweepSteps; ++s)
     for (int i = 0; i < 32; ++i)

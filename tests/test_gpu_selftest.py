@@ -247,3 +247,137 @@ def test_pattern_check_wrong_seed_counts_every_element_of_a_tail(P):
     r = P.hbm_pattern_check(0, n * 16, SEED, 1, [], SEED + 1, GUARD)
     assert r["errors"] == n, r["errors"]
     assert len(r["first"]) == 16 and r["guard_ok"] is True
+
+
+# ----------------------------------------------------------------------------- launch spans
+# A pass is one launch after another (selftest_host.h: launch_spans), each below the 2^32
+# work-items HIP supports. fill_launch_blocks / verify_launch_blocks move the seams between the
+# launches, separately: a seam bug that fill and verify shared would otherwise hide itself.
+SEAM_N = 7 * 1024 + 5            # elements: with 3 blocks a launch, seams at elements 3072 and 6144 and a partial last block
+MAX_LAUNCH_BLOCKS = 1 << 22
+GIB = 1 << 30
+ODD_BLOCKS = 65535               # an odd chunk size: its seams do not sit on powers of two
+ODD_CHUNK = ODD_BLOCKS * 1024 * 16
+
+
+def _launches(n_elements: int, blocks: int) -> int:
+    per = (blocks or MAX_LAUNCH_BLOCKS) * 1024
+    return -(-n_elements // per)
+
+
+@pytest.mark.parametrize("fill,verify", [(3, 3), (3, 0), (0, 3), (1, 2)])
+def test_pattern_check_is_clean_across_launch_seams(P, fill, verify):
+    r = P.hbm_pattern_check(0, SEAM_N * 16, SEED, 2, [], None, GUARD, fill_launch_blocks=fill,
+                            verify_launch_blocks=verify)
+    assert r["bytes"] == SEAM_N * 16 and r["errors"] == 0 and r["first"] == [], r
+    assert r["guard_ok"] is True
+    assert (r["fill_launches"], r["verify_launches"]) == (_launches(SEAM_N, fill), _launches(SEAM_N, verify))
+
+
+@pytest.mark.parametrize("verify", [3, 1])
+def test_split_verify_visits_every_element_exactly_once(P, verify):
+    r = P.hbm_pattern_check(0, SEAM_N * 16, SEED, 1, [], SEED + 1, GUARD, fill_launch_blocks=0,
+                            verify_launch_blocks=verify)
+    assert r["errors"] == SEAM_N, r["errors"]
+    assert len(r["first"]) == 16 and r["guard_ok"] is True
+    assert r["verify_launches"] == _launches(SEAM_N, verify)
+
+
+def _check_corruption(P, nbytes, corrupt, blocks, guard=0):
+    """One pass with `corrupt` applied: every corrupted element is counted once and reported at its
+    exact offset with the twin's expected word."""
+    from nanogpu.probe.selftest import pattern_at
+
+    assert len({o // 16 for o, _ in corrupt}) == len(corrupt) <= 16       # distinct elements, all reported
+    r = P.hbm_pattern_check(0, nbytes, SEED, 1, corrupt, None, guard, fill_launch_blocks=blocks,
+                            verify_launch_blocks=blocks)
+    assert r["errors"] == len(corrupt), r
+    assert [f[0] for f in r["first"]] == sorted(o for o, _ in corrupt)
+    xor = dict(corrupt)
+    for off, expected, got in r["first"]:
+        assert expected == pattern_at(off, SEED, 0), hex(off)
+        assert got == expected ^ (xor[off] << (8 * (off % 4))), hex(off)
+    return r
+
+
+def test_pattern_check_reports_corruption_on_both_sides_of_a_seam(P):
+    nbytes = SEAM_N * 16
+    corrupt = [(3 * 1024 * 16 - 1, 0x80), (3 * 1024 * 16, 0x01), (6 * 1024 * 16, 0x10), (nbytes - 1, 0x04)]
+    r = _check_corruption(P, nbytes, corrupt, 3, GUARD)
+    assert r["errors"] == 4 and r["guard_ok"] is True
+
+
+def _need_free(P, nbytes):
+    free, total = P.mem_info(0)
+    if free < nbytes + 2 * GIB:
+        pytest.skip(f"{free} of {total} bytes free: the test needs {nbytes} + 2 GiB = {nbytes + 2 * GIB}")
+
+
+def test_pattern_check_across_byte_offset_2_to_the_32(P):
+    nbytes = 4 * GIB + 1024 * 16 + 80
+    _need_free(P, nbytes)
+    seam = round((1 << 32) / ODD_CHUNK) * ODD_CHUNK                       # the launch seam nearest to 2^32
+    assert 0 < abs(seam - (1 << 32)) < ODD_CHUNK // 2 and seam % 16 == 0
+    corrupt = [(0, 0x01), ((1 << 32) - 1, 0x80), (1 << 32, 0x02), (seam, 0x10), (nbytes - 1, 0x04)]
+    r = _check_corruption(P, nbytes, corrupt, ODD_BLOCKS)
+    assert r["errors"] == 5
+    assert r["fill_launches"] == r["verify_launches"] == _launches(nbytes // 16, ODD_BLOCKS) == 5
+    r = P.hbm_pattern_check(0, nbytes, SEED, 2)                           # production chunking
+    assert r["bytes"] == nbytes and r["errors"] == 0 and r["first"] == [], r
+    assert r["fill_launches"] == r["verify_launches"] == 1
+
+
+def test_pattern_check_across_word_index_2_to_the_32(P):
+    """Past byte 2^34 the word index 4 i + k has a non-zero high half, so the expected words there
+    are the first ones the device computes through pattern_word's `(w >> 32) * kHiMul` term."""
+    from nanogpu.probe.selftest import pattern_at
+
+    nbytes = 16 * GIB + 1024 * 16 + 80
+    _need_free(P, nbytes)
+    seam = round((1 << 34) / ODD_CHUNK) * ODD_CHUNK
+    assert 0 < abs(seam - (1 << 34)) < ODD_CHUNK // 2 and seam % 16 == 0
+    corrupt = [((1 << 34) - 1, 0x80), (1 << 34, 0x02), ((1 << 34) + 16, 0x01), (seam, 0x10), (nbytes - 1, 0x04)]
+    for off in ((1 << 34), (1 << 34) + 16, nbytes - 1):                   # the high half is in these words
+        assert pattern_at(off, SEED, 0) != pattern_at(off - (1 << 34), SEED, 0)
+    r = _check_corruption(P, nbytes, corrupt, ODD_BLOCKS)
+    assert r["fill_launches"] == r["verify_launches"] == _launches(nbytes // 16, ODD_BLOCKS) == 17
+    r = P.hbm_pattern_check(0, nbytes, SEED, 2)                           # production chunking
+    assert r["bytes"] == nbytes and r["errors"] == 0 and r["first"] == [], r
+
+
+def test_pattern_check_past_the_first_production_launch(P):
+    """64 GiB and a bit, production chunking: the second launch starts at element 2^32, the one
+    size at which a `first` cut to 32 bits anywhere on its way into the pattern would show. The
+    expected words there are the device's, compared with the twin's."""
+    nbytes = 64 * GIB + 1024 * 16 + 80
+    _need_free(P, nbytes)
+    corrupt = [(0, 0x01), ((1 << 36) - 1, 0x80), (1 << 36, 0x02), ((1 << 36) + 1024 * 16, 0x10), (nbytes - 1, 0x04)]
+    r = _check_corruption(P, nbytes, corrupt, 0)
+    assert r["fill_launches"] == r["verify_launches"] == 2
+
+
+@pytest.mark.parametrize("blocks", [-1, MAX_LAUNCH_BLOCKS + 1])
+def test_launch_blocks_outside_their_range_are_refused(P, blocks):
+    with pytest.raises(ValueError):
+        P.hbm_pattern_check(0, 16, SEED, 1, fill_launch_blocks=blocks)
+    with pytest.raises(ValueError):
+        P.hbm_pattern_check(0, 16, SEED, 1, verify_launch_blocks=blocks)
+    r = P.hbm_pattern_check(0, 16, SEED, 1, fill_launch_blocks=MAX_LAUNCH_BLOCKS, verify_launch_blocks=MAX_LAUNCH_BLOCKS)
+    assert r["errors"] == 0
+
+
+def test_a_copy_of_2_to_the_32_work_items_is_refused_before_it_allocates(P):
+    """256 GiB is 2^24 blocks of 256 threads: no such launch is supported. The refusal comes
+    before the buffers: two of 256 GiB do not fit the device, and a failed allocation would be
+    a RuntimeError (copy_check: a MemoryError of the host's), not a ValueError."""
+    with pytest.raises(ValueError):
+        P.hbm_bandwidth(0, 256 << 30, 1)
+    with pytest.raises(ValueError):
+        P.copy_check(0, 4 << 34)
+    with pytest.raises(ValueError):
+        P.hbm_colocated(0, [[]], 256 << 30, 1)
+    with pytest.raises(ValueError):
+        P.mixed_colocated(0, [], [], 256 << 30, 1)
+    if P.device_count() > 1:
+        with pytest.raises(ValueError):
+            P.peer_bandwidth(0, 1, 256 << 30, 1)

@@ -5,6 +5,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import pytest
+
 from nanogpu import types as T
 from nanogpu.agent import cumask
 from nanogpu.agent.metrics import render as render_metrics
@@ -89,9 +91,21 @@ def test_pattern_twin_pins():
     assert S.pattern_at(16 * 4095 + 7, 0x1234ABCD, 1) == 0x72A42E3D
 
 
+@pytest.mark.parametrize("off", [5, 4095 * 16 + 7, (1 << 36) + 12345])
+def test_pattern_differs_across_every_address_line(off):
+    """The aliasing claim, for every line: a word and the word at the address with bit b flipped
+    differ, in both passes. Bits 2..33 flip the low half of the word index (mix32 is a bijection),
+    bits 34..47 the high half (HI_MUL is odd)."""
+    seed = 0x1234ABCD
+    for b in range(2, 48):
+        for p in (0, 1):
+            assert S.pattern_at(off, seed, p) != S.pattern_at(off ^ (1 << b), seed, p), (off, b, p)
+
+
 def test_native_header_agrees_with_the_twin():
-    """The kernels take the pattern, the expected tile and the record decode from
-    native/include/nanogpu/selftest_host.h; its stand-alone check pins the same values."""
+    """The kernels take the pattern, the launch spans, the expected tile and the record decode from
+    native/include/nanogpu/selftest_host.h; its stand-alone check pins the same values and
+    checks the spans."""
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "native"))
     import build  # native/build.py
 
@@ -101,6 +115,16 @@ def test_native_header_agrees_with_the_twin():
     src = (Path(build.NATIVE) / "tests" / "selftest_host_main.cpp").read_text().lower()
     for _, want in PINS[1:]:
         assert f"0x{want:08x}u" in src
+
+
+def test_host_program_passes_under_asan_and_ubsan():
+    """The same stand-alone program, launch spans up to 304 GiB included, under ASan + UBSan."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "native"))
+    import build  # native/build.py
+
+    r = subprocess.run([str(build.build_selftest_host("asan"))], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "selftest host arithmetic ok" in r.stdout
 
 
 # ----------------------------------------------------------------------------- fake probe
