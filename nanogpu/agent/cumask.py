@@ -16,6 +16,11 @@ behind an XCD it owns alone. A CPX partition is one XCD, so its unit is one CU.
 Sizing is floor(p/100 * units) (at least one unit), so any set of grants whose percents
 sum to <= 100 fits; bf16 MFMA throughput scales linearly with the granted CUs
 (tests/test_gpu.py::test_cu_mask_spatial_share_scales).
+
+A device may carry a *fence*: units the agent's self-test took out of circulation because one of
+their CUs fails (agent.node, `--selftest-fence`). Fenced units are never granted, grants are sized
+from the usable units, and a grant that held a unit before it was fenced keeps it until its pod
+ends (`fenced_in_use`). Without a fence every number here is what it was before fences existed.
 """
 from __future__ import annotations
 
@@ -27,6 +32,8 @@ class DeviceCUs:
     cus: int = 256
     xcds: int = 8
     used: dict[str, list[int]] = field(default_factory=dict)   # owner -> unit indices
+    fenced: set[int] = field(default_factory=set)              # units no grant may take (a CU of theirs fails)
+    short_grants: int = 0                                      # grants that got fewer units than their size
 
     @property
     def unit(self) -> int:
@@ -36,23 +43,43 @@ class DeviceCUs:
     def n_units(self) -> int:
         return self.cus // self.unit
 
+    def fence(self, units) -> None:
+        """Takes `units` out of circulation. A grant that holds one keeps it (`fenced_in_use`)."""
+        self.fenced |= {int(u) for u in units if 0 <= int(u) < self.n_units}
+
+    def usable_units(self) -> list[int]:
+        return [u for u in range(self.n_units) if u not in self.fenced]
+
+    def usable_bits(self) -> list[int]:
+        return [u * self.unit + k for u in self.usable_units() for k in range(self.unit)]
+
+    def fenced_in_use(self) -> list[str]:
+        """Owners of a grant that overlaps the fence: sized before it, or restored over it."""
+        return sorted(o for o, us in self.used.items() if self.fenced.intersection(us))
+
     def units_for(self, percent: int) -> int:
+        n = len(self.usable_units()) if self.fenced else self.n_units
         if percent >= 100:
-            return self.n_units
-        return max(1, (percent * self.n_units) // 100)
+            return n
+        return max(1, (percent * n) // 100)
 
     def free_units(self) -> list[int]:
-        taken = {u for us in self.used.values() for u in us}
+        taken = {u for us in self.used.values() for u in us} | self.fenced
         return [u for u in range(self.n_units) if u not in taken]
 
     def grant(self, owner: str, percent: int) -> list[int] | None:
-        """Returns the CU bit indices granted to `owner` (idempotent), or None if full."""
+        """Returns the CU bit indices granted to `owner` (idempotent), or None if full. On a
+        fenced device, grants sized before the fence may leave a later one less than its size:
+        it then takes the free units that remain (at least one) and `short_grants` counts it."""
         if owner in self.used:
             return self.bits(owner)
         need = self.units_for(percent)
         free = self.free_units()
         if len(free) < need:
-            return None
+            if not self.fenced or not free:
+                return None
+            need = len(free)
+            self.short_grants += 1
         self.used[owner] = free[:need]
         return self.bits(owner)
 

@@ -25,6 +25,12 @@ format, joined with what it granted:
   per device, when the deep self-test also ran matrix paths (--selftest-paths; absent otherwise)
     nanogpu_selftest_paths_checked{device}                           paths the last run checked on every CU
     nanogpu_selftest_path_cus_failed{device,path}                    CUs that failed that path
+  per device, only with --selftest-fence (agent/node.py: a failing CU's mask unit is fenced, not the GPU)
+    nanogpu_selftest_fenced_cus{device}                              CUs in fenced units
+    nanogpu_selftest_fenced_units_in_use{device}                     fenced units a grant from before still holds
+    nanogpu_selftest_short_grants_total{device}                      grants that got fewer units than their size
+    nanogpu_selftest_localise_seconds{device}                        the last localisation (absent before one)
+    nanogpu_selftest_runs_total{device,result="fenced"}              runs that ended with a new fence
 
 A pod's utilisation is its share of its device's busy time: the container's CUs over the
 device's CUs, times `nanogpu_device_busy_percent` (spatial sharing gives each tenant its own
@@ -52,9 +58,10 @@ def _read_int(p: Path) -> int | None:
 
 
 def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root: str = "",
-           selftest: dict | None = None) -> str:
-    """Prometheus text exposition of the node's devices and the plugin's live grants, and of
-    the deep self-test (`NodeAgent.selftest_stats`) once one has run."""
+           selftest: dict | None = None, fence: dict | None = None) -> str:
+    """Prometheus text exposition of the node's devices and the plugin's live grants, of the
+    deep self-test (`NodeAgent.selftest_stats`) once one has run, and of the fences
+    (`NodeAgent.fence_metrics()`: None, and nothing added, without --selftest-fence)."""
     devs = topo.devices
     minors = render_minors or [128 + 8 * i for i in range(len(devs))]
     health = plugin.health if plugin is not None else [bool(d.healthy) for d in devs]
@@ -167,6 +174,19 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
         family("nanogpu_selftest_path_cus_failed", "gauge", "CUs that failed the matrix path in the last deep self-test",
                [(_labels(device=i, path=name), len(p["failed"].get(name, [])))
                 for i, p in with_paths for name in p["checked"]])
+    if fence is not None:
+        def per_device(key):
+            return [(_labels(device=i), v) for i, v in sorted(fence.get(key, {}).items())]
+
+        family("nanogpu_selftest_fenced_cus", "gauge", "CUs in the CU-mask units the self-test fenced: never granted",
+               per_device("fenced_cus"))
+        family("nanogpu_selftest_fenced_units_in_use", "gauge",
+               "fenced units a grant from before the fence still holds, until its pod ends", per_device("units_in_use"))
+        family("nanogpu_selftest_short_grants_total", "counter",
+               "grants on a fenced device that got fewer units than their size", per_device("short_grants"))
+        family("nanogpu_selftest_localise_seconds", "gauge",
+               "duration of the device's last localisation of a failing sweep over its units",
+               per_device("localise_seconds"))
     return "\n".join(out) + "\n"
 
 
@@ -176,7 +196,7 @@ async def serve_metrics(agent, host: str = "0.0.0.0", port: int = 9410):
 
     async def metrics(_req):
         text = render(agent.topo, agent.plugin, agent.render_minors(), agent.sysfs_root,
-                      getattr(agent, "selftest_stats", None))
+                      getattr(agent, "selftest_stats", None), getattr(agent, "fence_metrics", lambda: None)())
         return web.Response(text=text, content_type="text/plain", charset="utf-8")
 
     async def healthz(_req):

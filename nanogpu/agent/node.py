@@ -108,6 +108,27 @@ def status_patch(topo: NodeTopology, advertise_percent: bool) -> dict:
     return {"status": {"capacity": dict(res), "allocatable": dict(res)}}
 
 
+def carry_fences(topo: NodeTopology, old: NodeTopology) -> dict[int, list[int]]:
+    """Copies into `topo` the fences `old` (the node's published topology) holds for the same
+    silicon: a device whose GPU has the same non-zero `unique_id` and that has the same part,
+    CUs and XCDs. A replaced GPU, or one whose partition mode changed, sheds its fence. A fence
+    is a statement about the silicon, so all of it is carried, whatever `--selftest-fence` allows
+    now: that number only bounds what this agent adds. Unit indices the device does not have are
+    dropped. Returns {device index: units} of what was carried."""
+    uid = {g.index: g.unique_id for g in old.gpus}
+    was = {(uid.get(d.gpu, 0), d.part): d for d in old.devices if d.fenced and uid.get(d.gpu, 0)}
+    now = {g.index: g.unique_id for g in topo.gpus}
+    carried = {}
+    for i, d in enumerate(topo.devices):
+        o = was.get((now.get(d.gpu, 0), d.part))
+        if o is not None and (o.cus, o.xcds) == (d.cus, d.xcds):
+            n_units = d.cus // max(1, d.xcds)
+            d.fenced = sorted({int(u) for u in o.fenced if 0 <= int(u) < n_units})
+            if d.fenced:
+                carried[i] = d.fenced
+    return carried
+
+
 async def publish(api, node_name: str, topo: NodeTopology, advertise_percent: bool) -> None:
     await api.patch_node(node_name, node_patch(topo))
     await api.patch_node_status(node_name, status_patch(topo, advertise_percent))
@@ -118,7 +139,8 @@ class NodeAgent:
                  device_plugin: bool = True, plugin_dir: str = "", health_period_s: float = 10.0,
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
-                 selftest_period_s: float = 0.0, selftest_paths=None):
+                 selftest_period_s: float = 0.0, selftest_paths=None, selftest_fence: int = 0,
+                 selftest_fence_reset: bool = False):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -139,6 +161,18 @@ class NodeAgent:
         if self.selftest_paths:
             self.selftest_deep = True            # the paths are part of the deep sweep
         self._no_paths_logged = False
+        # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
+        # CU-mask units that hold them (at most this many a device) instead of its health (`_deep_fenced`)
+        self.selftest_fence = max(0, int(selftest_fence))
+        self.selftest_fence_reset = selftest_fence_reset   # start without the fences the node's annotation holds
+        if self.selftest_fence:
+            self.selftest_deep = True
+        self._fence_proposed: dict[int, list[int]] = {}    # device -> units, from a run until the loop applies them
+        self.localise_seconds: dict[int, float] = {}       # device -> its last localisation, for /metrics
+        # device -> {(pod uid, container): units} of the whole-device grants that held the device
+        # when those units were fenced: they got no mask for them and run there until their pods end
+        self.whole_over_fence: dict[int, dict[tuple[str, str], set[int]]] = {}
+        self._fence_unpublished = False                    # a fence's node patch failed: sent again at the next run
         self.selftest_stats: dict | None = None  # last deep report per device, for /metrics
         self._no_deep_logged = False
         # kubelet's pod-resources API: which container got which device IDs (plugin.reconcile)
@@ -164,6 +198,8 @@ class NodeAgent:
         from ..k8s.informer import Informer
         from .plugin import NanoGpuPlugin
 
+        if self.selftest_fence and not self.selftest_fence_reset:
+            await self._carry_fences()
         await publish(self.api, self.node, self.topo, advertise_percent=not self.device_plugin)
         if not self.device_plugin:
             return
@@ -186,6 +222,19 @@ class NodeAgent:
             self.tasks.append(asyncio.ensure_future(self._health_loop()))
         if self.reconcile_period_s > 0 and self.pod_resources_socket:
             self.tasks.append(asyncio.ensure_future(self._reconcile_loop()))
+
+    async def _carry_fences(self) -> None:
+        """Before the first publish: the fences this node's annotation holds stay on the GPUs
+        they were measured on (`carry_fences`). A node that cannot be read carries nothing."""
+        try:
+            node = await self.api.get_node(self.node)
+            ann = ((node.get("metadata") or {}).get("annotations") or {}).get(T.ANNOTATION_TOPOLOGY)
+            carried = carry_fences(self.topo, NodeTopology.from_json(ann)) if ann else {}
+        except Exception as e:
+            log.warning("agent %s: no fences carried over, the node's topology could not be read: %s", self.node, e)
+            return
+        for i, units in sorted(carried.items()):
+            log.warning("agent %s: device %d starts with units %s fenced (carried over)", self.node, i, units)
 
     async def reconcile_now(self) -> list[tuple[str, str]]:
         """One pass: kubelet's pod-resources List against the plugin's grants."""
@@ -281,6 +330,9 @@ class NodeAgent:
         if changed:
             log.warning("agent %s: devices %s health changed", self.node, changed)
             await self.api.patch_node(self.node, node_patch(self.topo))
+            self._fence_unpublished = False
+        else:
+            await self._publish_fences(False)
         return changed
 
     def run_selftest(self, P=None) -> list[int] | None:
@@ -329,7 +381,8 @@ class NodeAgent:
         whole = any(i in a.devices and (len(a.devices) > 1 or a.percent >= 100 or not a.cus)
                     for a in self.plugin.grants.values())
         if not whole and not dc.used:
-            return None, True
+            # a fenced unit is never swept again, and the HBM check runs on the usable CUs
+            return (dc.usable_bits(), True) if dc.fenced else (None, True)
         free = dc.free_units()
         if whole or not free or not self._is_spx(i):
             return None
@@ -357,16 +410,132 @@ class NodeAgent:
                 self._no_paths_logged = True
                 log.warning("agent %s: this probe has no cu_sweep_paths: the deep self-test runs without the "
                             "matrix paths", self.node)
-            r = reports[i] = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths)
+            fenced_now = False
+            if self.selftest_fence and self.plugin is not None and self._is_spx(i):
+                r, fenced_now = self._deep_fenced(P, i, bits, nbytes)
+            else:
+                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths)
+            reports[i] = r
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
             st = self.selftest_stats
             st["reports"][i], st["at"][i] = r.to_dict(), time.time()
-            key = (i, "pass" if r.ok else "fail")
+            key = (i, "fenced" if fenced_now else "pass" if r.ok else "fail")
             st["runs"][key] = st["runs"].get(key, 0) + 1
             if not r.ok:
                 log.warning("agent %s: deep self-test failed on device %d: %s", self.node, i, r.describe_failure())
         return reports
+
+    def _deep_fenced(self, P, i: int, bits: list[int] | None, nbytes: int):
+        """The deep test of whole GPU `i` in fence mode (`--selftest-fence`), on the executor's
+        thread: (the report that decides the device, whether it proposes a new fence).
+
+        The sweep runs alone; only a clean chip (or what is usable of it) judges HBM. A failing
+        sweep that names CUs (`fenceable`) is localised over the plan's units. When every failed
+        CU failed again in a unit swept alone, and the device's fence stays within
+        `selftest_fence` units, one verification run over the plan's bits less those units
+        (with the HBM check, where the plan allowed it) decides: clean, and with no record from a
+        CU that failed, the device passes and the units are proposed for `_fence_locally`.
+        Anything else fails the device as without the flag."""
+        from ..probe.selftest import deep_selftest, failed_cus, fenceable, localise_failure
+
+        dc = self.plugin.cus[i]
+        paths = self.selftest_paths
+        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths)
+        if sweep.ok:
+            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths) if nbytes else sweep), False
+        if not fenceable(sweep):
+            return sweep, False
+        all_bits = bits if bits is not None else list(range(dc.cus))
+        units = sorted({b // dc.unit for b in all_bits} - dc.fenced)
+        loc = localise_failure(P, i, sweep, units, dc.unit, paths)
+        self.localise_seconds[i] = loc.seconds
+        bad = set(loc.bad_units)
+        why = (f"CUs {loc.unexplained} failed and no unit swept alone explains them" if loc.unexplained
+               else "no unit failed when swept alone" if not bad
+               else f"units {sorted(dc.fenced | bad)} are more than the {self.selftest_fence} this agent may fence"
+               if len(dc.fenced | bad) > self.selftest_fence else "")
+        if why:
+            sweep.notes.append("not fenced: " + why)
+            log.warning("agent %s: device %d is not fenced: %s", self.node, i, why)
+            return sweep, False
+        verify = deep_selftest(P, i, cu_mask_bits=[b for b in all_bits if b // dc.unit not in bad],
+                               hbm_bytes=nbytes, paths=paths)
+        stray = sorted(set(verify.cu_keys) & failed_cus(sweep))
+        if verify.ok and stray:
+            verify.ok = False
+            verify.notes.append(f"the sweep masked to the fence still ran on failed CUs {stray}")
+        if not verify.ok:
+            log.warning("agent %s: device %d: the verification without units %s failed: %s", self.node, i,
+                        sorted(bad), verify.describe_failure() or "; ".join(verify.notes))
+            return verify, False
+        verify.notes.append(f"units {sorted(bad)} fenced: {sweep.describe_failure()}")
+        self._fence_proposed[i] = sorted(bad)
+        return verify, True
+
+    def _whole_grants(self, i: int) -> list[tuple[str, str]]:
+        """Keys of the plugin's grants that hold device `i` whole (no CU mask of their own)."""
+        return sorted(k for k, a in self.plugin.grants.items()
+                      if i in a.devices and (len(a.devices) > 1 or a.percent >= 100 or not a.cus))
+
+    def _fence_locally(self) -> bool:
+        """On the event loop, after a run, without a call that can fail: what `_deep_fenced`
+        proposed goes into the plugin's CU maps and the topology. A grant that arrived during the
+        run keeps what it got until its pod ends: a fractional one its now-fenced unit
+        (`fenced_in_use`), a whole-device one the whole device, answered before there was a fence
+        to mask (`whole_over_fence`). Both are logged and counted. True when a fence was added."""
+        proposed, self._fence_proposed = self._fence_proposed, {}
+        if not proposed or self.plugin is None:
+            return False
+        for i, units in sorted(proposed.items()):
+            dc = self.plugin.cus[i]
+            dc.fence(units)
+            self.topo.devices[i].fenced = sorted(dc.fenced)
+            log.warning("agent %s: device %d: units %s fenced, %d of %d CUs stay usable", self.node, i, units,
+                        len(dc.usable_bits()), dc.cus)
+            if dc.fenced_in_use():
+                log.warning("agent %s: device %d: grants %s hold fenced units until their pods end", self.node, i,
+                            dc.fenced_in_use())
+            whole = self._whole_grants(i)
+            for k in whole:
+                self.whole_over_fence.setdefault(i, {}).setdefault(k, set()).update(units)
+            if whole:
+                log.warning("agent %s: device %d: whole-device grants %s arrived before units %s were fenced and "
+                            "run on every CU until their pods end", self.node, i, whole, units)
+        return True
+
+    async def _publish_fences(self, added: bool) -> None:
+        """The node's annotation gets the fences, after the health of this run is applied. A
+        patch that fails is logged and sent again at the next run or health check, so one API
+        error neither hides a failed device nor loses a fence for good."""
+        if not (added or self._fence_unpublished):
+            return
+        try:
+            await self.api.patch_node(self.node, node_patch(self.topo))
+            self._fence_unpublished = False
+        except Exception as e:
+            self._fence_unpublished = True
+            log.warning("agent %s: publishing the fences failed, to be sent again: %s", self.node, e)
+
+    def _fenced_units_in_use(self, i: int) -> int:
+        dc = self.plugin.cus[i]
+        held = {u for us in dc.used.values() for u in us}
+        for k, units in list(self.whole_over_fence.get(i, {}).items()):
+            if k in self.plugin.grants:
+                held |= units
+            else:
+                del self.whole_over_fence[i][k]        # its pod ended
+        return len(dc.fenced & held)
+
+    def fence_metrics(self) -> dict | None:
+        """What /metrics shows of the fences; None without `--selftest-fence` (then nothing is added)."""
+        if not self.selftest_fence:
+            return None
+        cus = self.plugin.cus if self.plugin is not None else []
+        return {"fenced_cus": {i: len(dc.fenced) * dc.unit for i, dc in enumerate(cus)},
+                "units_in_use": {i: self._fenced_units_in_use(i) for i in range(len(cus))},
+                "short_grants": {i: dc.short_grants for i, dc in enumerate(cus)},
+                "localise_seconds": dict(self.localise_seconds)}
 
     async def selftest(self, P=None) -> list[int] | None:
         """Runs the self-test off the event loop and applies it: failed devices become
@@ -375,7 +544,9 @@ class NodeAgent:
         if failed is None:
             return None
         self.selftest_failed = set(failed)
+        added = self._fence_locally()
         await self._apply_selftest()
+        await self._publish_fences(added)
         return failed
 
     async def _apply_selftest(self) -> None:
@@ -413,7 +584,9 @@ class NodeAgent:
         if failed is None:
             return None
         self.selftest_failed |= set(failed)
+        added = self._fence_locally()
         await self._apply_selftest()
+        await self._publish_fences(added)
         return failed
 
     async def _selftest_loop(self) -> None:
@@ -476,6 +649,21 @@ def build_parser():
                     help="the deep self-test also runs an exact MFMA chain of these matrix paths on every CU: "
                          "'all' or a comma-separated list of f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64 "
                          "(implies --selftest-deep; start-up and periodic runs alike)")
+    class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
+        def __call__(self, parser, ns, values, option_string=None):
+            if values < 0:
+                parser.error(f"{option_string}: a number of units, 0 or more")
+            ns.selftest_fence = values
+            if values:
+                ns.selftest = ns.selftest_deep = True
+
+    ap.add_argument("--selftest-fence", action=_Fence, type=int, default=0, metavar="UNITS",
+                    help="a whole GPU (SPX) whose deep self-test fails on CUs that fail again when swept alone stays "
+                         "Healthy and loses the CU-mask units (8 CUs, one per XCD, each) that hold them: at most UNITS "
+                         "a device, those carried over a restart included (0: off; implies --selftest-deep; needs "
+                         "the device plugin)")
+    ap.add_argument("--selftest-fence-reset", action="store_true",
+                    help="start without the fences the node's topology annotation holds")
     ap.add_argument("--selftest-hbm-mib", type=int, default=0,
                     help="cap of the deep self-test's HBM check in MiB (0: all free HBM less 2 GiB); "
                          "only devices without a grant are checked")
@@ -513,7 +701,8 @@ def main(argv: list[str] | None = None) -> int:
                           plugin_dir=a.plugin_dir, sysfs_root=a.sysfs_root,
                           pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
-                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths)
+                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths,
+                          selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset)
         await agent.start()
         if a.selftest:
             failed = await agent.selftest()

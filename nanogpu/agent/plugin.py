@@ -13,6 +13,8 @@ into a device inside the container. This is the AMD equivalent:
 * answers with the device nodes (`/dev/kfd` + the partition's `/dev/dri/renderD*`), a
   spatial CU mask for fractional grants (`HSA_CU_MASK`, XCD-symmetric, see cumask.py),
   and the HBM budget (`NANO_GPU_MEMORY_MIB`, enforced in-process by nanogpu.agent.guest);
+  on a device with fenced units (agent --selftest-fence) a fractional grant avoids them and a
+  whole-device grant gets `HSA_CU_MASK` with the usable CUs;
 * records the CU grant as `nano-gpu/cu-mask-<c>` on the pod, so an agent restart
   rebuilds its CU map from the API server (the same checkpoint contract as the
   extender's, reference dealer.go:58-72);
@@ -118,6 +120,8 @@ class NanoGpuPlugin:
         self.render = render_minors or [128 + 8 * i for i in range(len(topo.devices))]
         self.dev_root = dev_root
         self.cus = [cumask.DeviceCUs(d.cus, d.xcds) for d in topo.devices]
+        for dc, d in zip(self.cus, topo.devices):
+            dc.fence(d.fenced)               # units outside the device's range are dropped
         self.health = [bool(d.healthy) for d in topo.devices]
         self._changed = asyncio.Event()
         # live grants by (pod uid, container): what the agent's /metrics reports per container
@@ -327,13 +331,28 @@ class NanoGpuPlugin:
         mask_ann = "full"
         cus = 0
         if percent < T.GPU_PERCENT_EACH_CARD and len(devs) == 1:
-            bits = self.cus[devs[0]].grant(f"{pu.pod_uid(pod)}/{name}", percent)
+            dc = self.cus[devs[0]]
+            short = dc.short_grants
+            bits = dc.grant(f"{pu.pod_uid(pod)}/{name}", percent)
             if bits is None:
                 raise RuntimeError(f"device {devs[0]} has no free CUs for {percent}%")
+            if dc.short_grants != short:
+                log.warning("Allocate: %s/%s sized %d units on fenced device %d, %d were left: a short grant",
+                            pu.pod_key(pod), name, dc.units_for(percent), devs[0], len(bits) // dc.unit)
             mask_ann = cumask.hsa_cu_mask(0, bits)   # the container sees its device as index 0
             r.envs["HSA_CU_MASK"] = mask_ann
             r.envs["NANO_GPU_CUS"] = str(len(bits))
             cus = len(bits)
+        elif any(self.cus[d].fenced for d in devs):
+            # whole devices, one or more of them fenced: the mask keeps the tenant off the fenced
+            # units. The grant stays a whole-device one for the annotation, rebuild, reconcile and
+            # the self-test's plan (cus = 0, "full"). The runtime in the container never sees the
+            # placement annotation's order: it enumerates the render nodes it was given in its own
+            # order, so a device's index there is its rank among the container's devices sorted by
+            # physical index ("1,0" and "0,1" are the same container), as a lone device is index 0
+            r.envs["HSA_CU_MASK"] = ";".join(cumask.hsa_cu_mask(k, self.cus[d].usable_bits())
+                                             for k, d in enumerate(sorted(set(devs))) if self.cus[d].fenced)
+            r.envs["NANO_GPU_CUS"] = str(sum(len(self.cus[d].usable_bits()) for d in devs))
         if mib:
             r.envs["NANO_GPU_MEMORY_MIB"] = str(mib)
             total = self.topo.devices[devs[0]].hbm_mib if devs else 0

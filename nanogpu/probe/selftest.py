@@ -27,7 +27,13 @@ and Inf and NaN operands. Zero, subnormal and largest-normal operands and E8M0 s
 127 and 128 are outside the sweep's generators: `edge_tiles` puts them through `matrix_tile`, one
 wave on one CU, in the GPU tests only.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--json]` prints one report.
+`localise_failure` turns a failing sweep into CU-mask units (agent.cumask: one CU per XCD): it
+runs `deep_selftest` once per candidate unit, masked to it, and says which units fail again and
+which failing CUs no such unit explains. The agent fences those units (`--selftest-fence`)
+instead of failing the device when `fenceable` allows it.
+
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--json]` prints one report;
+with `--fence N` it also prints the units (at most N) an agent would fence, and changes nothing.
 """
 from __future__ import annotations
 
@@ -581,9 +587,13 @@ class DeepReport:
     seed: int = 0
     notes: list[str] = field(default_factory=list)
     paths: dict | None = None        # {"checked": [names], "failed": {name: [[xcc, cu_key], ...]}}; None: not run
+    cu_keys: list = field(default_factory=list, repr=False)   # sorted (xcc, cu_key) of every CU a record came from
 
     def to_dict(self) -> dict:
-        return asdict(self)
+        """What /metrics and --json show: every field but `cu_keys`, as before that field existed."""
+        d = asdict(self)
+        del d["cu_keys"]
+        return d
 
     def describe_failure(self) -> str:
         """What failed, for the agent's warning line."""
@@ -601,6 +611,20 @@ class DeepReport:
         return "; ".join(parts)
 
 
+def hbm_check_takes_mask(P) -> bool:
+    """Whether this probe's `hbm_pattern_check` has the `cu_mask` argument: read from the binding's
+    own signature (a Python stand-in's parameters, or the signature line pybind11 puts into the doc
+    string), never from an error's text, so that a refused argument stays an error."""
+    import inspect
+
+    f = P.hbm_pattern_check
+    try:
+        params = inspect.signature(f).parameters
+    except (TypeError, ValueError):            # a built-in without a text signature: its doc string has one
+        return "cu_mask" in (getattr(f, "__doc__", None) or "")
+    return "cu_mask" in params or any(p.kind is p.VAR_KEYWORD for p in params.values())
+
+
 def free_hbm_bytes(P, device: int, cap_mib: int = 0) -> int:
     """What the HBM check may take: the free memory less 2 GiB of headroom, capped by
     `cap_mib` when positive, in whole 16-byte elements."""
@@ -615,7 +639,8 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
                   seed: int | None = None, rounds: int = 4, paths=None) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
     the sweep to those CU-mask bits (the agent passes the units no tenant holds; None: the
-    whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory. `paths`
+    whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory, on a stream
+    with the same mask when one is given (a probe that cannot gets a note and no HBM check). `paths`
     (`parse_paths`: None, "all", "a,b" or a list of names) makes the sweep launches
     `cu_sweep_paths` with those matrix paths instead of `cu_sweep`: still one visit per CU.
     `ok` is false if and only if a CU failed a check or a path, HBM errors were counted, or
@@ -645,6 +670,7 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
             r *= 2
         sweep.update(lds_bytes=int(last["lds_bytes"]), launches=launches, ms=float(last["ms"]))
         rep.sweep = sweep
+        rep.cu_keys = sorted({(rec[0], cu_key(rec[1])) for rec in records})
         if names:
             rep.paths = {"checked": names, "failed": fold_paths(records, last["paths"], expected)["failed"]}
         if sweep["cus_uncovered"]:
@@ -654,8 +680,14 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
             for _ in range(MAX_LAUNCHES):      # memory taken by someone else meanwhile is no device fault
                 if want < 16:
                     break
+                if mask and not hbm_check_takes_mask(P):
+                    rep.notes.append("this probe's hbm_pattern_check takes no cu_mask: HBM was not checked "
+                                     "on the masked device")
+                    break
                 try:
-                    rep.hbm = dict(P.hbm_pattern_check(device, want, seed, 2))
+                    # the keyword only with a mask: a probe from before it is never called with it
+                    rep.hbm = dict(P.hbm_pattern_check(device, want, seed, 2, cu_mask=mask) if mask
+                                   else P.hbm_pattern_check(device, want, seed, 2))
                     break
                 except MemoryError:
                     rep.notes.append(f"{want} bytes of HBM could not be allocated")
@@ -667,6 +699,90 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         rep.ok, rep.error = False, f"{type(e).__name__}: {e}"
     rep.seconds = time.perf_counter() - t0
     return rep
+
+
+def failed_cus(report: DeepReport) -> set[tuple[int, int]]:
+    """The `(xcc, cu_key)` of every CU that failed a check or a matrix path in `report`."""
+    out = {(f["xcc"], f["cu_key"]) for f in (report.sweep or {}).get("failed", [])}
+    for where in ((report.paths or {}).get("failed") or {}).values():
+        out |= {(x, k) for x, k in where}
+    return out
+
+
+def fenceable(report: DeepReport) -> bool:
+    """Whether a failed report names CUs that a CU-mask fence could keep tenants off: no HIP
+    error, no HBM errors, no CU whose record is garbled (the `record` kind: then the CU's
+    identity is as doubtful as its result), and at least one failed CU or path."""
+    if report.error or (report.hbm and report.hbm.get("errors")):
+        return False
+    if any("record" in f["kinds"] for f in (report.sweep or {}).get("failed", [])):
+        return False
+    if "record" in ((report.paths or {}).get("failed") or {}):
+        return False
+    return bool(failed_cus(report))
+
+
+@dataclass
+class Localisation:
+    bad_units: list[int] = field(default_factory=list)      # units whose own masked sweep failed
+    unit_keys: dict = field(default_factory=dict)           # unit -> sorted [(xcc, cu_key)] its records came from
+    unexplained: list = field(default_factory=list)         # failed CUs of the report outside every bad unit
+    seconds: float = 0.0
+    launches: dict = field(default_factory=dict)            # unit -> sweep launches it took
+    uncovered: dict = field(default_factory=dict)           # unit -> CUs of it no launch reached (absent: 0)
+
+    def to_dict(self) -> dict:
+        return asdict(self)
+
+
+def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_size: int, paths=None,
+                     seed: int | None = None, rounds: int = 4) -> Localisation:
+    """Which CU-mask units hold the CUs that failed in `report`. Every unit of `candidate_units`
+    (unit u is mask bits [u * unit_size, (u + 1) * unit_size)) gets one `deep_selftest` masked to
+    it: the same `paths`, no HBM check, and the same re-launch for coverage. A unit is bad when
+    that run is not ok. `unexplained` lists the failed CUs of `report` that no bad unit's sweep
+    ran on: a failure that did not come back, or a mask that does not reach where it lives.
+    Either way a fence of the bad units would not cover it."""
+    t0 = time.perf_counter()
+    loc = Localisation()
+    for u in sorted(set(candidate_units)):
+        bits = [u * unit_size + k for k in range(unit_size)]
+        r = deep_selftest(P, device, cu_mask_bits=bits, seed=seed, rounds=rounds, paths=paths)
+        loc.unit_keys[u] = list(r.cu_keys)
+        if r.sweep:
+            loc.launches[u] = r.sweep["launches"]
+            if r.sweep["cus_uncovered"]:
+                loc.uncovered[u] = r.sweep["cus_uncovered"]
+        if not r.ok:
+            loc.bad_units.append(u)
+    explained = {k for u in loc.bad_units for k in loc.unit_keys[u]}
+    loc.unexplained = sorted(failed_cus(report) - explained)
+    loc.seconds = time.perf_counter() - t0
+    return loc
+
+
+def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None) -> dict:
+    """What `--fence N` prints: {"units", "cus" (unit -> its CUs), "reason" (when no unit),
+    "seconds"}. Only a whole MI355X: the unit is one CU on each of its 8 XCDs."""
+    from .. import types as T
+
+    out = {"units": [], "cus": {}, "reason": "", "seconds": 0.0}
+    cus = int(P.device_props(device)["cus"])
+    if cus != T.MI355X_CUS:
+        out["reason"] = f"{cus} CUs: the CU-mask units are measured on a whole MI355X ({T.MI355X_CUS} CUs) only"
+    elif not fenceable(report):
+        out["reason"] = "a HIP error, HBM errors or a garbled record are not a CU's to fence"
+    else:
+        loc = localise_failure(P, device, report, range(cus // T.MI355X_XCDS), T.MI355X_XCDS, paths)
+        out["seconds"] = loc.seconds
+        if loc.unexplained:
+            out["reason"] = f"failing CUs {loc.unexplained} did not fail again in any unit"
+        elif len(loc.bad_units) > max_units:
+            out["reason"] = f"{len(loc.bad_units)} units fail, more than {max_units}"
+        else:
+            out["units"] = loc.bad_units
+            out["cus"] = {str(u): [list(k) for k in loc.unit_keys[u]] for u in loc.bad_units}
+    return out
 
 
 def main(argv: list[str] | None = None) -> int:
@@ -682,6 +798,9 @@ def main(argv: list[str] | None = None) -> int:
                     help="HBM to pattern-check in MiB (default 1024; 0: all free memory less 2 GiB)")
     ap.add_argument("--paths", default="", metavar="all|LIST",
                     help="matrix paths every CU also runs: 'all' or a comma-separated list of " + ", ".join(PATHS))
+    ap.add_argument("--fence", type=int, default=0, metavar="N",
+                    help="after a failed sweep, print the CU-mask units (at most N) and CUs an agent started with "
+                         "--selftest-fence N would fence; changes nothing on the device or the node")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args(argv)
     try:
@@ -691,8 +810,9 @@ def main(argv: list[str] | None = None) -> int:
     P = probe(required=True)
     nbytes = free_hbm_bytes(P, a.device, a.hbm_mib)
     rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names)
+    plan = would_fence(P, a.device, rep, a.fence, names) if a.fence > 0 and not rep.ok else None
     if a.json:
-        print(json.dumps(rep.to_dict()))
+        print(json.dumps(dict(rep.to_dict(), fence=plan) if a.fence > 0 else rep.to_dict()))
     else:
         s, h = rep.sweep or {}, rep.hbm or {}
         print(f"device {a.device}: {'ok' if rep.ok else 'FAILED'} in {rep.seconds:.3f} s")
@@ -711,6 +831,13 @@ def main(argv: list[str] | None = None) -> int:
             print("  " + rep.describe_failure())
         for n in rep.notes:
             print("  note: " + n)
+        if plan is not None:
+            if plan["units"]:
+                print(f"  would fence {len(plan['units'])} unit(s) in {plan['seconds']:.3f} s:")
+                for u in plan["units"]:
+                    print(f"    unit {u}: " + ", ".join(f"(xcc {x}, key {k:#x})" for x, k in plan["cus"][str(u)]))
+            else:
+                print("  would fence nothing: " + plan["reason"])
     return 0 if rep.ok else 1
 
 

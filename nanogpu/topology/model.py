@@ -14,8 +14,11 @@ Schema (version 1):
   "virtualization": "BAREMETAL",
   "gpus":    [{"index": 0, "numa": 0, "cus": 256, "xcds": 8, "hbm_mib": 294912,
                "compute_partition": "SPX", "memory_partition": "NPS1", "bdf": "0000:05:00.0",
-               "hbm_busy_cal": [[25, 20.7], [100, 28.7]]}],   # optional (agent --calibrate)
-  "devices": [{"gpu": 0, "part": 0, "cus": 256, "xcds": 8, "hbm_mib": 294912}],
+               "hbm_busy_cal": [[25, 20.7], [100, 28.7]],     # optional (agent --calibrate)
+               "unique_id": 1234}],                           # only next to a fence (below)
+  "devices": [{"gpu": 0, "part": 0, "cus": 256, "xcds": 8, "hbm_mib": 294912,
+               "fenced": [5]}],                               # only when non-empty: CU-mask units
+                                                              # (agent.cumask) the agent's self-test fenced
   "link_bw": [[0.0, 153.0, ...], ...],     # GB/s between physical GPUs (0 = no direct link)
   "calibration": {...}                      # optional probe results (HBM GB/s, CU map)
 }
@@ -50,6 +53,9 @@ class GpuSpec:
     # the poller maps readings through it onto types.HBM_STREAMING_CURVE (telemetry.store
     # normalize_hbm_activity). Empty: readings are taken as they are.
     hbm_busy_cal: list = field(default_factory=list)
+    # KFD's unique_id of the chip (0: unknown). Published only for a GPU that has a fenced device:
+    # a restarted agent keeps a fence only on the chip it was measured on (agent.node.carry_fences)
+    unique_id: int = 0
 
 
 @dataclass
@@ -62,6 +68,9 @@ class DeviceSpec:
     healthy: bool = True         # False: never chosen (uncorrectable RAS errors, device gone)
     pool: int = -1               # shared HBM pool (memory partition) id within the node, -1 = own HBM
     mib_share: int = 0           # HBM a whole-device grant takes from the pool (pool / members)
+    # CU-mask units (agent.cumask: one CU per XCD each) the agent's self-test took out of
+    # circulation; the device stays schedulable and still counts 100 gpu-percent
+    fenced: list[int] = field(default_factory=list)
 
 
 @dataclass
@@ -77,11 +86,14 @@ class NodeTopology:
 
     # --- serialisation -------------------------------------------------------------
     def to_dict(self) -> dict:
+        # a topology without a fence serialises as it did before fences existed
+        fenced_gpus = {d.gpu for d in self.devices if d.fenced}
         return {
             "version": self.version, "model": self.model, "gfx": self.gfx,
             "virtualization": self.virtualization,
-            "gpus": [g.__dict__ for g in self.gpus],
-            "devices": [d.__dict__ for d in self.devices],
+            "gpus": [{k: v for k, v in g.__dict__.items()
+                      if k != "unique_id" or (v and g.index in fenced_gpus)} for g in self.gpus],
+            "devices": [{k: v for k, v in d.__dict__.items() if k != "fenced" or v} for d in self.devices],
             "link_bw": self.link_bw,
             "calibration": self.calibration,
         }
@@ -212,7 +224,7 @@ def from_host_json(host: str | dict, max_ue: int = 0) -> NodeTopology:
                 index=parent, numa=int(g.get("numa", -1)), cus=0, xcds=0, hbm_mib=0,
                 compute_partition=cp, memory_partition=(g.get("memory_partition") or "").upper(),
                 xgmi_peers=int(g.get("xgmi_peers", 0)), xgmi_link_gbs=float(g.get("xgmi_min_bw_mbs", 0)) / 1000.0,
-                ras_ue=int(g.get("ras_ue", 0)), ras_ce=int(g.get("ras_ce", 0)),
+                ras_ue=int(g.get("ras_ue", 0)), ras_ce=int(g.get("ras_ce", 0)), unique_id=int(g.get("unique_id", 0)),
                 bdf=f"{int(g.get('domain', 0)):04x}:{(loc >> 8) & 0xff:02x}:{(loc >> 3) & 0x1f:02x}.{loc & 7}")
         gs = gpus_by_parent[parent]
         gs.cus += int(g.get("cus", 0))
@@ -268,7 +280,16 @@ def from_node(node: dict) -> NodeTopology:
     return fallback_topology(count)
 
 
+def usable_cus(d: DeviceSpec) -> int:
+    """CUs of the device outside its fence: a fenced unit is one CU on each of its XCDs."""
+    return d.cus - len(set(d.fenced)) * max(1, d.xcds)
+
+
 def describe(t: NodeTopology) -> dict[str, Any]:
-    return {"gpus": t.n_gpus, "devices": len(t.devices),
-            "partition": t.gpus[0].compute_partition if t.gpus else "",
-            "hbm_mib_total": sum(d.hbm_mib for d in t.devices), "gfx": t.gfx}
+    out = {"gpus": t.n_gpus, "devices": len(t.devices),
+           "partition": t.gpus[0].compute_partition if t.gpus else "",
+           "hbm_mib_total": sum(d.hbm_mib for d in t.devices), "gfx": t.gfx}
+    fenced = {i: f"{usable_cus(d)}/{d.cus}" for i, d in enumerate(t.devices) if d.fenced}
+    if fenced:
+        out["fenced"] = fenced       # device index -> usable / total CUs
+    return out

@@ -1236,9 +1236,12 @@ uint64_t launch_blocks_arg(long long v) {
 // (tests) puts the buffer between two guard regions, see kGuardByte. A pass is one launch after
 // another on one stream (st::launch_spans), each below 2^32 work-items, under one pair of events;
 // `fill_launch_blocks` / `verify_launch_blocks` (tests) move the seams between them, separately.
+// `cu_mask` (empty: every CU) is the CU mask of that stream, as in the sweep: the agent's mask of
+// a device with fenced units, so that no fenced CU writes or judges the pattern.
 PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes,
                                 const std::vector<std::pair<uint64_t, uint32_t>>& corrupt, int64_t verify_seed,
-                                size_t guard_bytes, long long fill_launch_blocks, long long verify_launch_blocks) {
+                                size_t guard_bytes, long long fill_launch_blocks, long long verify_launch_blocks,
+                                const std::vector<uint32_t>& cu_mask) {
   HIP_OK(hipSetDevice(dev));
   check_guard_bytes(guard_bytes);
   if (bytes == 0 || bytes % 16 != 0) throw std::invalid_argument("hbm_pattern_check: bytes must be a positive multiple of 16");
@@ -1272,7 +1275,7 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
     HIP_OK(hipDeviceSynchronize());   // the kernels run on a stream that does not wait for the null stream
   }
   DevBuf<VerifyOut> vo(1);
-  Stream stream({});
+  Stream stream(cu_mask);
   Events ev;
   HIP_OK(hipMemsetAsync(vo.p, 0, sizeof(VerifyOut), stream.s));
   // n = 0 touches no memory: loads both kernels outside the timed spans
@@ -1656,13 +1659,13 @@ PYBIND11_MODULE(_probe, m) {
       "hbm_pattern_check",
       [](int dev, size_t bytes, uint32_t seed, int passes, const std::vector<std::pair<uint64_t, uint32_t>>& corrupt,
          const py::object& verify_seed, size_t guard_bytes, long long fill_launch_blocks,
-         long long verify_launch_blocks) {
+         long long verify_launch_blocks, const std::vector<uint32_t>& cu_mask) {
         const int64_t vseed = verify_seed.is_none() ? int64_t(-1) : int64_t(verify_seed.cast<uint32_t>());
         PatternResult r;
         {
           py::gil_scoped_release nogil;
           r = hbm_pattern_check(dev, bytes, seed, passes, corrupt, vseed, guard_bytes, fill_launch_blocks,
-                                verify_launch_blocks);
+                                verify_launch_blocks, cu_mask);
         }
         py::list first;
         for (const st::Mismatch& mm : r.first)
@@ -1681,7 +1684,7 @@ PYBIND11_MODULE(_probe, m) {
       py::arg("device") = 0, py::arg("bytes") = size_t(256) << 20, py::arg("seed") = 0x5eed5eedu,
       py::arg("passes") = 2, py::arg("corrupt") = std::vector<std::pair<uint64_t, uint32_t>>{},
       py::arg("verify_seed") = py::none(), py::arg("guard_bytes") = size_t(0), py::arg("fill_launch_blocks") = 0LL,
-      py::arg("verify_launch_blocks") = 0LL,
+      py::arg("verify_launch_blocks") = 0LL, py::arg("cu_mask") = std::vector<uint32_t>{},
       "Fills `bytes` of device memory with an address-derived pattern and verifies it (odd passes: the "
       "complement). errors counts mismatching 16-byte elements over all passes; first = up to 16 of "
       "(byte offset of the first differing byte, expected word, got word). corrupt = [(byte offset, xor byte)] "
@@ -1690,7 +1693,9 @@ PYBIND11_MODULE(_probe, m) {
       "wrote outside the buffer, or `corrupt` named an offset in the guard behind it (bytes <= offset < bytes + guard_bytes). A pass is one launch after another of at most 2^22 blocks (64 GiB), "
       "each below the 2^32 work-items HIP supports; fill_launches / verify_launches count them per pass. Test hook: "
       "fill_launch_blocks / verify_launch_blocks = blocks of 1,024 elements a launch of the fill / of the verify "
-      "(0: 2^22; 1..2^22; anything else raises ValueError). Raises MemoryError when the buffer cannot be allocated.");
+      "(0: 2^22; 1..2^22; anything else raises ValueError). cu_mask = 32-bit words of a CU mask (as cu_sweep's): the fill, "
+      "the verify and the clearing of their result run on a stream masked to those CUs; empty: an unmasked stream, "
+      "every CU. Raises MemoryError when the buffer cannot be allocated.");
   m.def(
       "mem_info",
       [](int dev) {
