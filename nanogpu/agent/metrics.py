@@ -25,6 +25,8 @@ format, joined with what it granted:
   per device, when the deep self-test also ran matrix paths (--selftest-paths; absent otherwise)
     nanogpu_selftest_paths_checked{device}                           paths the last run checked on every CU
     nanogpu_selftest_path_cus_failed{device,path}                    CUs that failed that path
+  per device, when the deep self-test also ran the vector-ALU part (--selftest-valu; absent otherwise)
+    nanogpu_selftest_valu_checked{device}                            groups the last run checked on every CU
   per device, only with --selftest-fence (agent/node.py: a failing CU's mask unit is fenced, not the GPU)
     nanogpu_selftest_fenced_cus{device}                              CUs in fenced units
     nanogpu_selftest_fenced_units_in_use{device}                     fenced units a grant from before still holds
@@ -174,6 +176,9 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
         family("nanogpu_selftest_path_cus_failed", "gauge", "CUs that failed the matrix path in the last deep self-test",
                [(_labels(device=i, path=name), len(p["failed"].get(name, [])))
                 for i, p in with_paths for name in p["checked"]])
+        family("nanogpu_selftest_valu_checked", "gauge",
+               "vector-ALU groups (with approx and regs) the last deep self-test ran on every CU",
+               [(_labels(device=i), len(r["valu"]["checked"])) for i, r in reps if r.get("valu")])
     if fence is not None:
         def per_device(key):
             return [(_labels(device=i), v) for i, v in sorted(fence.get(key, {}).items())]

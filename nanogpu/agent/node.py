@@ -140,7 +140,7 @@ class NodeAgent:
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
                  selftest_period_s: float = 0.0, selftest_paths=None, selftest_fence: int = 0,
-                 selftest_fence_reset: bool = False):
+                 selftest_fence_reset: bool = False, selftest_valu=None):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -161,6 +161,12 @@ class NodeAgent:
         if self.selftest_paths:
             self.selftest_deep = True            # the paths are part of the deep sweep
         self._no_paths_logged = False
+        # vector-ALU groups, 'approx' and 'regs' every deep sweep also runs (probe.selftest_valu.parse_valu)
+        from ..probe.selftest_valu import parse_valu
+
+        self.selftest_valu: list[str] = parse_valu(selftest_valu)
+        if self.selftest_valu:
+            self.selftest_deep = True
         # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
         # CU-mask units that hold them (at most this many a device) instead of its health (`_deep_fenced`)
         self.selftest_fence = max(0, int(selftest_fence))
@@ -414,7 +420,7 @@ class NodeAgent:
             if self.selftest_fence and self.plugin is not None and self._is_spx(i):
                 r, fenced_now = self._deep_fenced(P, i, bits, nbytes)
             else:
-                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths)
+                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths, valu=self.selftest_valu)
             reports[i] = r
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
@@ -441,14 +447,15 @@ class NodeAgent:
 
         dc = self.plugin.cus[i]
         paths = self.selftest_paths
-        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths)
+        valu = self.selftest_valu
+        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths, valu=valu)
         if sweep.ok:
-            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths) if nbytes else sweep), False
+            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths, valu=valu) if nbytes else sweep), False
         if not fenceable(sweep):
             return sweep, False
         all_bits = bits if bits is not None else list(range(dc.cus))
         units = sorted({b // dc.unit for b in all_bits} - dc.fenced)
-        loc = localise_failure(P, i, sweep, units, dc.unit, paths)
+        loc = localise_failure(P, i, sweep, units, dc.unit, paths, valu=valu)
         self.localise_seconds[i] = loc.seconds
         bad = set(loc.bad_units)
         why = (f"CUs {loc.unexplained} failed and no unit swept alone explains them" if loc.unexplained
@@ -460,7 +467,7 @@ class NodeAgent:
             log.warning("agent %s: device %d is not fenced: %s", self.node, i, why)
             return sweep, False
         verify = deep_selftest(P, i, cu_mask_bits=[b for b in all_bits if b // dc.unit not in bad],
-                               hbm_bytes=nbytes, paths=paths)
+                               hbm_bytes=nbytes, paths=paths, valu=valu)
         stray = sorted(set(verify.cu_keys) & failed_cus(sweep))
         if verify.ok and stray:
             verify.ok = False
@@ -649,6 +656,23 @@ def build_parser():
                     help="the deep self-test also runs an exact MFMA chain of these matrix paths on every CU: "
                          "'all' or a comma-separated list of f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64 "
                          "(implies --selftest-deep; start-up and periodic runs alike)")
+    class _Valu(argparse.Action):              # --selftest-valu implies --selftest-deep
+        def __call__(self, parser, ns, values, option_string=None):
+            from ..probe.selftest_valu import parse_valu
+
+            try:
+                ns.selftest_valu = parse_valu(values)
+            except ValueError as e:
+                parser.error(f"{option_string}: {e}")
+            if not ns.selftest_valu:
+                parser.error(f"{option_string}: name at least one group, or 'all'")
+            ns.selftest = ns.selftest_deep = True
+
+    ap.add_argument("--selftest-valu", action=_Valu, default=[], metavar="all|LIST",
+                    help="the deep self-test also runs, on all four SIMDs of every CU, exact chains of vector-ALU "
+                         "instructions, the transcendentals and a pattern test of the vector register file: 'all' or a "
+                         "comma-separated list of fma32, fma64, pkfma16, pkfma32, addmul32, int32, int64, bits, dot, "
+                         "cvt, xlane, approx, regs (implies --selftest-deep; start-up and periodic runs alike)")
     class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
         def __call__(self, parser, ns, values, option_string=None):
             if values < 0:
@@ -701,7 +725,7 @@ def main(argv: list[str] | None = None) -> int:
                           plugin_dir=a.plugin_dir, sysfs_root=a.sysfs_root,
                           pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
-                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths,
+                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths, selftest_valu=a.selftest_valu,
                           selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset)
         await agent.start()
         if a.selftest:

@@ -32,7 +32,7 @@ runs `deep_selftest` once per candidate unit, masked to it, and says which units
 which failing CUs no such unit explains. The agent fences those units (`--selftest-fence`)
 instead of failing the device when `fenceable` allows it.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--json]` prints one report;
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--json]` prints one report;
 with `--fence N` it also prints the units (at most N) an agent would fence, and changes nothing.
 """
 from __future__ import annotations
@@ -588,11 +588,16 @@ class DeepReport:
     notes: list[str] = field(default_factory=list)
     paths: dict | None = None        # {"checked": [names], "failed": {name: [[xcc, cu_key], ...]}}; None: not run
     cu_keys: list = field(default_factory=list, repr=False)   # sorted (xcc, cu_key) of every CU a record came from
+    # {"checked": [names], "failed": {kind: [[xcc, cu_key], ...]}, "cus": fold_valu's, "reg_slots", "ms"}; None: not run
+    valu: dict | None = field(default=None, repr=False)
 
     def to_dict(self) -> dict:
-        """What /metrics and --json show: every field but `cu_keys`, as before that field existed."""
+        """What /metrics and --json show: every field but `cu_keys`, as before that field existed;
+        `valu` only when the vector-ALU part ran."""
         d = asdict(self)
         del d["cu_keys"]
+        if d["valu"] is None:
+            del d["valu"]
         return d
 
     def describe_failure(self) -> str:
@@ -604,6 +609,9 @@ class DeepReport:
                  for f in (self.sweep or {}).get("failed", [])]
         for name, where in sorted(((self.paths or {}).get("failed") or {}).items()):
             parts.append(f"matrix path {name} on " + ", ".join(f"CU (xcc {x}, key {k:#x})" for x, k in where))
+        for c in (self.valu or {}).get("cus", []):
+            at = f" at slot {c['bad_slot']}, wave {c['bad_wave']} lane {c['bad_lane']}" if c["bad_slot"] >= 0 else ""
+            parts.append(f"vector ALU {'+'.join(c['kinds'])} on CU (xcc {c['xcc']}, key {c['cu_key']:#x}){at}")
         if self.hbm and self.hbm.get("errors"):
             first = self.hbm.get("first") or []
             at = f", first at byte {first[0][0]} (expected {first[0][1]:#010x}, got {first[0][2]:#010x})" if first else ""
@@ -636,15 +644,19 @@ def free_hbm_bytes(P, device: int, cap_mib: int = 0) -> int:
 
 
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
-                  seed: int | None = None, rounds: int = 4, paths=None) -> DeepReport:
+                  seed: int | None = None, rounds: int = 4, paths=None, valu=None) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
     the sweep to those CU-mask bits (the agent passes the units no tenant holds; None: the
     whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory, on a stream
     with the same mask when one is given (a probe that cannot gets a note and no HBM check). `paths`
     (`parse_paths`: None, "all", "a,b" or a list of names) makes the sweep launches
     `cu_sweep_paths` with those matrix paths instead of `cu_sweep`: still one visit per CU.
-    `ok` is false if and only if a CU failed a check or a path, HBM errors were counted, or
-    HIP raised."""
+    `valu` (`selftest_valu.parse_valu`) makes each launch of the coverage loop be followed by a
+    `cu_sweep_valu` launch of those vector-ALU groups on the same mask.
+    `ok` is false if and only if a CU failed a check, a path or a vector-ALU group, HBM errors
+    were counted, or HIP raised."""
+    from .selftest_valu import fold_valu, parse_valu
+
     from ..agent import cumask
 
     if seed is None:
@@ -654,16 +666,24 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
     if names and not hasattr(P, "cu_sweep_paths"):
         rep.notes.append("this probe has no cu_sweep_paths: the plain sweep ran and no matrix path was checked")
         names = []
+    vnames = parse_valu(valu)
+    if vnames and not hasattr(P, "cu_sweep_valu"):
+        rep.notes.append("this probe has no cu_sweep_valu: no vector-ALU group was checked")
+        vnames = []
     t0 = time.perf_counter()
     try:
         cus = int(P.device_props(device)["cus"])
         mask = cumask.mask_words(cu_mask_bits, cus) if cu_mask_bits is not None else []
         expected = len(set(cu_mask_bits)) if cu_mask_bits is not None else cus
         records, launches, r, last = [], 0, rounds, {}
+        vrecords, vlast = [], {}
         while True:
             last = P.cu_sweep_paths(device, mask, r, seed, names) if names else P.cu_sweep(device, mask, r, seed)
             launches += 1
             records.extend(last["records"])
+            if vnames:
+                vlast = P.cu_sweep_valu(device, mask, r, seed, vnames)
+                vrecords.extend(vlast["records"])
             sweep = fold_sweep([rec[:5] for rec in records], expected)
             if sweep["cus_uncovered"] == 0 or launches >= MAX_LAUNCHES:
                 break
@@ -673,6 +693,13 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         rep.cu_keys = sorted({(rec[0], cu_key(rec[1])) for rec in records})
         if names:
             rep.paths = {"checked": names, "failed": fold_paths(records, last["paths"], expected)["failed"]}
+        if vnames:
+            vf = fold_valu(vrecords, vlast["groups"], expected)
+            rep.valu = {"checked": vnames, "failed": vf["failed"], "cus": vf["cus"], "reg_slots": int(vlast["reg_slots"]),
+                        "ms": float(vlast["ms"])}
+            rep.cu_keys = sorted(set(rep.cu_keys) | {(rec[0], cu_key(rec[1])) for rec in vrecords})
+            if vf["cus_uncovered"]:
+                rep.notes.append(f"{vf['cus_uncovered']} CUs not reached by the vector-ALU launches")
         if sweep["cus_uncovered"]:
             rep.notes.append(f"{sweep['cus_uncovered']} CUs not reached in {launches} launches")
         if hbm_bytes > 0:
@@ -693,7 +720,7 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
                     rep.notes.append(f"{want} bytes of HBM could not be allocated")
                     want = (want // 2) & ~15
         rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
-                  and not (rep.paths and rep.paths["failed"]))
+                  and not (rep.paths and rep.paths["failed"]) and not (rep.valu and rep.valu["failed"]))
     except Exception as e:                     # a HIP error is a failed device
         log.exception("deep self-test of device %d raised", device)
         rep.ok, rep.error = False, f"{type(e).__name__}: {e}"
@@ -704,8 +731,9 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
 def failed_cus(report: DeepReport) -> set[tuple[int, int]]:
     """The `(xcc, cu_key)` of every CU that failed a check or a matrix path in `report`."""
     out = {(f["xcc"], f["cu_key"]) for f in (report.sweep or {}).get("failed", [])}
-    for where in ((report.paths or {}).get("failed") or {}).values():
-        out |= {(x, k) for x, k in where}
+    for part in (report.paths, report.valu):
+        for where in ((part or {}).get("failed") or {}).values():
+            out |= {(x, k) for x, k in where}
     return out
 
 
@@ -717,7 +745,7 @@ def fenceable(report: DeepReport) -> bool:
         return False
     if any("record" in f["kinds"] for f in (report.sweep or {}).get("failed", [])):
         return False
-    if "record" in ((report.paths or {}).get("failed") or {}):
+    if "record" in ((report.paths or {}).get("failed") or {}) or "record" in ((report.valu or {}).get("failed") or {}):
         return False
     return bool(failed_cus(report))
 
@@ -736,10 +764,10 @@ class Localisation:
 
 
 def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_size: int, paths=None,
-                     seed: int | None = None, rounds: int = 4) -> Localisation:
+                     seed: int | None = None, rounds: int = 4, valu=None) -> Localisation:
     """Which CU-mask units hold the CUs that failed in `report`. Every unit of `candidate_units`
     (unit u is mask bits [u * unit_size, (u + 1) * unit_size)) gets one `deep_selftest` masked to
-    it: the same `paths`, no HBM check, and the same re-launch for coverage. A unit is bad when
+    it: the same `paths` and `valu`, no HBM check, and the same re-launch for coverage. A unit is bad when
     that run is not ok. `unexplained` lists the failed CUs of `report` that no bad unit's sweep
     ran on: a failure that did not come back, or a mask that does not reach where it lives.
     Either way a fence of the bad units would not cover it."""
@@ -747,7 +775,7 @@ def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_s
     loc = Localisation()
     for u in sorted(set(candidate_units)):
         bits = [u * unit_size + k for k in range(unit_size)]
-        r = deep_selftest(P, device, cu_mask_bits=bits, seed=seed, rounds=rounds, paths=paths)
+        r = deep_selftest(P, device, cu_mask_bits=bits, seed=seed, rounds=rounds, paths=paths, valu=valu)
         loc.unit_keys[u] = list(r.cu_keys)
         if r.sweep:
             loc.launches[u] = r.sweep["launches"]
@@ -761,7 +789,7 @@ def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_s
     return loc
 
 
-def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None) -> dict:
+def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None, valu=None) -> dict:
     """What `--fence N` prints: {"units", "cus" (unit -> its CUs), "reason" (when no unit),
     "seconds"}. Only a whole MI355X: the unit is one CU on each of its 8 XCDs."""
     from .. import types as T
@@ -773,7 +801,7 @@ def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None) 
     elif not fenceable(report):
         out["reason"] = "a HIP error, HBM errors or a garbled record are not a CU's to fence"
     else:
-        loc = localise_failure(P, device, report, range(cus // T.MI355X_XCDS), T.MI355X_XCDS, paths)
+        loc = localise_failure(P, device, report, range(cus // T.MI355X_XCDS), T.MI355X_XCDS, paths, valu=valu)
         out["seconds"] = loc.seconds
         if loc.unexplained:
             out["reason"] = f"failing CUs {loc.unexplained} did not fail again in any unit"
@@ -798,19 +826,24 @@ def main(argv: list[str] | None = None) -> int:
                     help="HBM to pattern-check in MiB (default 1024; 0: all free memory less 2 GiB)")
     ap.add_argument("--paths", default="", metavar="all|LIST",
                     help="matrix paths every CU also runs: 'all' or a comma-separated list of " + ", ".join(PATHS))
+    ap.add_argument("--valu", default="", metavar="all|LIST",
+                    help="vector-ALU groups, 'approx' and 'regs' every CU also runs: 'all' or a comma-separated list")
     ap.add_argument("--fence", type=int, default=0, metavar="N",
                     help="after a failed sweep, print the CU-mask units (at most N) and CUs an agent started with "
                          "--selftest-fence N would fence; changes nothing on the device or the node")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args(argv)
     try:
+        from .selftest_valu import parse_valu
+
         names = parse_paths(a.paths)
+        vnames = parse_valu(a.valu)
     except ValueError as e:
         ap.error(str(e))
     P = probe(required=True)
     nbytes = free_hbm_bytes(P, a.device, a.hbm_mib)
-    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names)
-    plan = would_fence(P, a.device, rep, a.fence, names) if a.fence > 0 and not rep.ok else None
+    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names, valu=vnames)
+    plan = would_fence(P, a.device, rep, a.fence, names, valu=vnames) if a.fence > 0 and not rep.ok else None
     if a.json:
         print(json.dumps(dict(rep.to_dict(), fence=plan) if a.fence > 0 else rep.to_dict()))
     else:
@@ -823,6 +856,11 @@ def main(argv: list[str] | None = None) -> int:
         if rep.paths:
             bad = rep.paths["failed"]
             print(f"  matrix paths {', '.join(rep.paths['checked'])}: "
+                  + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
+        if rep.valu:
+            bad = rep.valu["failed"]
+            print(f"  vector ALU {', '.join(rep.valu['checked'])} ({rep.valu['reg_slots']} registers a lane, "
+                  f"{rep.valu['ms']:.3f} ms): "
                   + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
