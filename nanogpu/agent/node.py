@@ -154,19 +154,18 @@ class NodeAgent:
         self.selftest_deep = selftest_deep       # probe.selftest.deep_selftest instead of gpu_selftest
         self.selftest_hbm_mib = selftest_hbm_mib  # cap of the HBM pattern check (0: free HBM less 2 GiB)
         self.selftest_period_s = selftest_period_s
-        # matrix paths every deep sweep also runs (probe.selftest.parse_paths: "all", "a,b" or names)
         from ..probe.selftest import parse_paths
-
-        self.selftest_paths: list[str] = parse_paths(selftest_paths)
-        if self.selftest_paths:
-            self.selftest_deep = True            # the paths are part of the deep sweep
-        self._no_paths_logged = False
-        # vector-ALU groups, 'approx' and 'regs' every deep sweep also runs (probe.selftest_valu.parse_valu)
         from ..probe.selftest_valu import parse_valu
 
-        self.selftest_valu: list[str] = parse_valu(selftest_valu)
-        if self.selftest_valu:
-            self.selftest_deep = True
+        def part_of_deep(parse, spec) -> list[str]:   # "all", "a,b" or names; any of them makes the sweep deep
+            names = parse(spec)
+            if names:
+                self.selftest_deep = True
+            return names
+
+        self.selftest_paths = part_of_deep(parse_paths, selftest_paths)   # matrix paths every deep sweep also runs
+        self._no_paths_logged = False
+        self.selftest_valu = part_of_deep(parse_valu, selftest_valu)      # vector-ALU groups, 'approx' and 'regs'
         # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
         # CU-mask units that hold them (at most this many a device) instead of its health (`_deep_fenced`)
         self.selftest_fence = max(0, int(selftest_fence))
@@ -640,35 +639,27 @@ def build_parser():
     ap.add_argument("--selftest-deep", action=_Deep, nargs=0, default=False,
                     help="the start-up self-test checks every CU (MFMA pipes, LDS) and the free HBM with an "
                          "address-derived pattern instead of one tile and 16 MiB (implies --selftest)")
-    class _Paths(argparse.Action):             # --selftest-paths implies --selftest-deep
-        def __call__(self, parser, ns, values, option_string=None):
-            from ..probe.selftest import parse_paths
+    from ..probe.selftest import parse_paths
+    from ..probe.selftest_valu import parse_valu
 
-            try:
-                ns.selftest_paths = parse_paths(values)
-            except ValueError as e:
-                parser.error(f"{option_string}: {e}")
-            if not ns.selftest_paths:
-                parser.error(f"{option_string}: name at least one path, or 'all'")
-            ns.selftest = ns.selftest_deep = True
+    def names_action(parse, noun: str):        # --selftest-paths and --selftest-valu imply --selftest-deep
+        class _Names(argparse.Action):
+            def __call__(self, parser, ns, values, option_string=None):
+                try:
+                    setattr(ns, self.dest, parse(values))
+                except ValueError as e:
+                    parser.error(f"{option_string}: {e}")
+                if not getattr(ns, self.dest):
+                    parser.error(f"{option_string}: name at least one {noun}, or 'all'")
+                ns.selftest = ns.selftest_deep = True
 
-    ap.add_argument("--selftest-paths", action=_Paths, default=[], metavar="all|LIST",
+        return _Names
+
+    ap.add_argument("--selftest-paths", action=names_action(parse_paths, "path"), default=[], metavar="all|LIST",
                     help="the deep self-test also runs an exact MFMA chain of these matrix paths on every CU: "
                          "'all' or a comma-separated list of f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64 "
                          "(implies --selftest-deep; start-up and periodic runs alike)")
-    class _Valu(argparse.Action):              # --selftest-valu implies --selftest-deep
-        def __call__(self, parser, ns, values, option_string=None):
-            from ..probe.selftest_valu import parse_valu
-
-            try:
-                ns.selftest_valu = parse_valu(values)
-            except ValueError as e:
-                parser.error(f"{option_string}: {e}")
-            if not ns.selftest_valu:
-                parser.error(f"{option_string}: name at least one group, or 'all'")
-            ns.selftest = ns.selftest_deep = True
-
-    ap.add_argument("--selftest-valu", action=_Valu, default=[], metavar="all|LIST",
+    ap.add_argument("--selftest-valu", action=names_action(parse_valu, "group"), default=[], metavar="all|LIST",
                     help="the deep self-test also runs, on all four SIMDs of every CU, exact chains of vector-ALU "
                          "instructions, the transcendentals and a pattern test of the vector register file: 'all' or a "
                          "comma-separated list of fma32, fma64, pkfma16, pkfma32, addmul32, int32, int64, bits, dot, "

@@ -40,6 +40,8 @@ from __future__ import annotations
 import logging
 import time
 from dataclasses import asdict, dataclass, field
+from functools import reduce
+from operator import or_
 
 log = logging.getLogger(__name__)
 
@@ -100,6 +102,36 @@ def _coverage(seen, expected_cus) -> tuple[int, list, int]:
     return len(expected), uncovered, len(uncovered)
 
 
+def _by_cu(records) -> dict[tuple[int, int], list[list]]:
+    """Records that begin `(xcc, hw_id, ...)`, grouped: `{(xcc, cu_key): [a visit's other fields, ...]}`."""
+    by_cu: dict[tuple[int, int], list[list]] = {}
+    for xcc, hw_id, *rest in records:
+        by_cu.setdefault((xcc, cu_key(hw_id)), []).append(rest)
+    return by_cu
+
+
+def _or(values) -> int:
+    return reduce(or_, values, 0)
+
+
+def _simds_seen_min(by_cu, field: int) -> int:
+    return min((bin(_or(v[field] for v in visits)).count("1") for visits in by_cu.values()), default=0)
+
+
+def _named_failures(by_cu, expected_cus, failures) -> dict:
+    """The report of a fold whose failures have names. `failures` holds, per failed CU in key
+    order, `(key, the names it failed, what its entry of "cus" adds to xcc and cu_key)`."""
+    n_expected, uncovered, n_uncovered = _coverage(by_cu, expected_cus)
+    failed: dict[str, list[list[int]]] = {}
+    cus = []
+    for (xcc, key), names, entry in failures:
+        cus.append({"xcc": xcc, "cu_key": key, **entry})
+        for n in names:
+            failed.setdefault(n, []).append([xcc, key])
+    return {"cus_seen": len(by_cu), "cus_expected": n_expected, "failed": failed, "cus": cus,
+            "uncovered": [list(k) for k in uncovered], "cus_uncovered": n_uncovered}
+
+
 def fold_sweep(records, expected_cus) -> dict:
     """Folds `cu_sweep` records `(xcc, hw_id, fail_bits, simds, lds_bad_off)` by CU.
 
@@ -108,22 +140,20 @@ def fold_sweep(records, expected_cus) -> dict:
     from (empty when only the number is known; `cus_uncovered` counts them either way). A CU is
     failed when any of its visits failed; `simds_seen_min` is the smallest number of distinct
     SIMDs any CU's waves reported."""
-    seen: dict[tuple[int, int], dict] = {}
-    for xcc, hw_id, fail, simds, bad in records:
-        c = seen.setdefault((xcc, cu_key(hw_id)), {"fail": 0, "simds": 0, "bad": -1})
-        c["fail"] |= fail
-        c["simds"] |= simds
-        if bad >= 0 and (c["bad"] < 0 or bad < c["bad"]):
-            c["bad"] = bad
-    n_expected, uncovered, n_uncovered = _coverage(seen, expected_cus)
+    by_cu = _by_cu(records)
+    n_expected, uncovered, n_uncovered = _coverage(by_cu, expected_cus)
     per_xcd: dict[int, int] = {}
-    for xcc, _ in seen:
+    for xcc, _ in by_cu:
         per_xcd[xcc] = per_xcd.get(xcc, 0) + 1
-    failed = [{"xcc": k[0], "cu_key": k[1], "kinds": fail_kinds(c["fail"]), "lds_bad_off": c["bad"]}
-              for k, c in sorted(seen.items()) if c["fail"]]
-    return {"cus_seen": len(seen), "cus_expected": n_expected, "per_xcd": dict(sorted(per_xcd.items())),
+    failed = []
+    for k, visits in sorted(by_cu.items()):
+        fail = _or(fail for fail, _simds, _bad in visits)
+        if fail:
+            failed.append({"xcc": k[0], "cu_key": k[1], "kinds": fail_kinds(fail),
+                           "lds_bad_off": min((bad for _fail, _simds, bad in visits if bad >= 0), default=-1)})
+    return {"cus_seen": len(by_cu), "cus_expected": n_expected, "per_xcd": dict(sorted(per_xcd.items())),
             "failed": failed, "uncovered": [list(k) for k in uncovered], "cus_uncovered": n_uncovered,
-            "simds_seen_min": min((bin(c["simds"]).count("1") for c in seen.values()), default=0)}
+            "simds_seen_min": _simds_seen_min(by_cu, 1)}
 
 
 # ---- matrix paths: the Python twin of native/include/nanogpu/selftest_paths_host.h -------------
@@ -142,16 +172,21 @@ SCALED_PATHS = ("mxfp8", "mxfp6", "mxfp4")
 SCALE_WINDOW = (127, 128)
 
 
-def parse_paths(spec) -> list[str]:
-    """None / "" / [] -> [], "all" -> every path, "a,b" or a list of names -> those, in bit
-    order. Raises ValueError on an unknown name."""
+def _parse_names(spec, known, noun: str) -> list[str]:
+    """None / "" / [] -> [], "all" -> every name of `known`, "a,b" or a list of names -> those,
+    in bit order. Raises ValueError on an unknown name."""
     if not spec:
         return []
-    names = list(PATHS) if spec == "all" else [n.strip() for n in spec.split(",")] if isinstance(spec, str) else list(spec)
-    bad = [n for n in names if n not in PATHS]
+    names = list(known) if spec == "all" else [n.strip() for n in spec.split(",")] if isinstance(spec, str) else list(spec)
+    bad = [n for n in names if n not in known]
     if bad or not names:
-        raise ValueError(f"unknown matrix path(s) {bad}: choose from {', '.join(PATHS)} or 'all'")
-    return [n for n in PATHS if n in names]
+        raise ValueError(f"unknown {noun}(s) {bad}: choose from {', '.join(known)} or 'all'")
+    return [n for n in known if n in names]
+
+
+def parse_paths(spec) -> list[str]:
+    """`_parse_names` over `PATHS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
+    return _parse_names(spec, PATHS, "matrix path")
 
 
 def path_dim(path: str) -> int:
@@ -552,27 +587,14 @@ def fold_paths(records, paths, expected_cus) -> dict:
     to its `[xcc, cu_key]` list, `cus` lists per failed CU its paths and the waves (bit w: wave
     w) that saw one fail; `uncovered` / `cus_uncovered` as in `fold_sweep`: not a failure."""
     paths = list(paths)
-    seen: dict[tuple[int, int], list[int]] = {}
-    for xcc, hw_id, _fail, _simds, _bad, pfail, pwaves in records:
-        c = seen.setdefault((xcc, cu_key(hw_id)), [0, 0])
-        c[0] |= pfail
-        c[1] |= pwaves
-    n_expected, uncovered, n_uncovered = _coverage(seen, expected_cus)
-
-    def names(bits: int) -> list[str]:
-        out = [paths[i] for i in range(len(paths)) if bits >> i & 1]
-        return out + (["record"] if bits >> len(paths) else [])
-
-    failed: dict[str, list[list[int]]] = {}
-    cus = []
-    for k, (bits, waves) in sorted(seen.items()):
-        if not bits:
-            continue
-        cus.append({"xcc": k[0], "cu_key": k[1], "paths": names(bits), "waves": waves})
-        for n in names(bits):
-            failed.setdefault(n, []).append([k[0], k[1]])
-    return {"cus_seen": len(seen), "cus_expected": n_expected, "failed": failed, "cus": cus,
-            "uncovered": [list(k) for k in uncovered], "cus_uncovered": n_uncovered}
+    by_cu = _by_cu(records)
+    failures = []
+    for k, visits in sorted(by_cu.items()):
+        bits = _or(v[3] for v in visits)
+        if bits:
+            names = [p for i, p in enumerate(paths) if bits >> i & 1] + (["record"] if bits >> len(paths) else [])
+            failures.append((k, names, {"paths": names, "waves": _or(v[4] for v in visits)}))
+    return _named_failures(by_cu, expected_cus, failures)
 
 
 @dataclass
@@ -643,6 +665,27 @@ def free_hbm_bytes(P, device: int, cap_mib: int = 0) -> int:
     return n & ~15
 
 
+def _hbm_check(P, device: int, hbm_bytes: int, seed: int, mask: list[int], notes: list[str]) -> dict | None:
+    """`hbm_pattern_check`'s report for `hbm_bytes`, or for the half, or the quarter, where that
+    much cannot be allocated; on a stream masked to `mask` when it is not empty. None where nothing
+    was checked; `notes` gets every allocation that failed and a probe that takes no mask."""
+    want = hbm_bytes & ~15
+    for _ in range(MAX_LAUNCHES):      # memory taken by someone else meanwhile is no device fault
+        if want < 16:
+            break
+        if mask and not hbm_check_takes_mask(P):
+            notes.append("this probe's hbm_pattern_check takes no cu_mask: HBM was not checked on the masked device")
+            break
+        try:
+            # the keyword only with a mask: a probe from before it is never called with it
+            return dict(P.hbm_pattern_check(device, want, seed, 2, cu_mask=mask) if mask
+                        else P.hbm_pattern_check(device, want, seed, 2))
+        except MemoryError:
+            notes.append(f"{want} bytes of HBM could not be allocated")
+            want = (want // 2) & ~15
+    return None
+
+
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
                   seed: int | None = None, rounds: int = 4, paths=None, valu=None) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
@@ -703,22 +746,7 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         if sweep["cus_uncovered"]:
             rep.notes.append(f"{sweep['cus_uncovered']} CUs not reached in {launches} launches")
         if hbm_bytes > 0:
-            want = hbm_bytes & ~15
-            for _ in range(MAX_LAUNCHES):      # memory taken by someone else meanwhile is no device fault
-                if want < 16:
-                    break
-                if mask and not hbm_check_takes_mask(P):
-                    rep.notes.append("this probe's hbm_pattern_check takes no cu_mask: HBM was not checked "
-                                     "on the masked device")
-                    break
-                try:
-                    # the keyword only with a mask: a probe from before it is never called with it
-                    rep.hbm = dict(P.hbm_pattern_check(device, want, seed, 2, cu_mask=mask) if mask
-                                   else P.hbm_pattern_check(device, want, seed, 2))
-                    break
-                except MemoryError:
-                    rep.notes.append(f"{want} bytes of HBM could not be allocated")
-                    want = (want // 2) & ~15
+            rep.hbm = _hbm_check(P, device, hbm_bytes, seed, mask, rep.notes)
         rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
                   and not (rep.paths and rep.paths["failed"]) and not (rep.valu and rep.valu["failed"]))
     except Exception as e:                     # a HIP error is a failed device
@@ -853,15 +881,15 @@ def main(argv: list[str] | None = None) -> int:
             print(f"  CUs checked {s['cus_seen']}/{s['cus_expected']} (per XCD {s['per_xcd']}), "
                   f"{len(s['failed'])} failed, {s['cus_uncovered']} not reached, LDS {s['lds_bytes']} B per CU, "
                   f"sweep {s['ms']:.3f} ms in {s['launches']} launch(es)")
+        def print_named(what: str, part: dict, detail: str = "") -> None:
+            bad = part["failed"]
+            print(f"  {what} {', '.join(part['checked'])}{detail}: "
+                  + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
+
         if rep.paths:
-            bad = rep.paths["failed"]
-            print(f"  matrix paths {', '.join(rep.paths['checked'])}: "
-                  + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
+            print_named("matrix paths", rep.paths)
         if rep.valu:
-            bad = rep.valu["failed"]
-            print(f"  vector ALU {', '.join(rep.valu['checked'])} ({rep.valu['reg_slots']} registers a lane, "
-                  f"{rep.valu['ms']:.3f} ms): "
-                  + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
+            print_named("vector ALU", rep.valu, f" ({rep.valu['reg_slots']} registers a lane, {rep.valu['ms']:.3f} ms)")
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
                   f"verify {h['verify_gbs']:.0f} GB/s, {h.get('verify_launches', 1)} launch(es) a pass")

@@ -13,7 +13,7 @@ import math
 import struct
 from fractions import Fraction
 
-from .selftest import M32, _coverage, cu_key, mix32, tile_checksum
+from .selftest import M32, _by_cu, _named_failures, _parse_names, _simds_seen_min, mix32, tile_checksum
 
 GROUPS = ("fma32", "fma64", "pkfma16", "pkfma32", "addmul32", "int32", "int64", "bits", "dot", "cvt", "xlane",
           "approx", "regs")                      # bit order of the records
@@ -35,15 +35,8 @@ F64, F32, F16, BF16, E4M3, E5M2 = (53, 11, 1023), (24, 8, 127), (11, 5, 15), (8,
 
 
 def parse_valu(spec) -> list[str]:
-    """None / "" / [] -> [], "all" -> every name, "a,b" or a list -> those, in bit order.
-    Raises ValueError on an unknown name."""
-    if not spec:
-        return []
-    names = list(GROUPS) if spec == "all" else [n.strip() for n in spec.split(",")] if isinstance(spec, str) else list(spec)
-    bad = [n for n in names if n not in GROUPS]
-    if bad or not names:
-        raise ValueError(f"unknown vector-ALU group(s) {bad}: choose from {', '.join(GROUPS)} or 'all'")
-    return [n for n in GROUPS if n in names]
+    """`_parse_names` over `GROUPS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
+    return _parse_names(spec, GROUPS, "vector-ALU group")
 
 
 def operand(group: str, s: int, lane: int, k: int) -> int:
@@ -492,39 +485,30 @@ def fold_valu(records, groups, expected_cus) -> dict:
     for r in records:
         counts[r[7]] = counts.get(r[7], 0) + 1
     majority = next((h for h, n in counts.items() if 2 * n > len(records)), None)
-    seen: dict[tuple[int, int], dict] = {}
-    for xcc, hw_id, fail, simds, gbits, slot, thread, ahash in records:
-        c = seen.setdefault((xcc, cu_key(hw_id)), {"kinds": set(), "waves": 0, "slot": -1, "thread": -1, "simds": 0})
-        c["simds"] |= simds
-        if fail >> 16 or gbits >> n_exact or bool(fail & FAIL_EXACT) != bool(gbits) or bool(fail & FAIL_REGS) != (slot >= 0):
-            c["kinds"].add("record")
-        c["kinds"].update(groups[i] for i in range(n_exact) if gbits >> i & 1)
-        if fail & FAIL_REGS:
-            c["kinds"].add("regs")
-            if slot >= 0 and (c["slot"] < 0 or (slot, thread) < (c["slot"], c["thread"])):
-                c["slot"], c["thread"] = slot, thread
-        if fail & (FAIL_BOUND | FAIL_HASH) or ahash != majority:
-            c["kinds"].add("approx")
-        if ahash != majority and not fail & (FAIL_BOUND | FAIL_HASH):
-            c["waves"] |= 0xF
-        c["waves"] |= (fail | fail >> 4 | fail >> 8 | fail >> 12) & 0xF
-    n_expected, uncovered, n_uncovered = _coverage(seen, expected_cus)
-    order = groups + ["record"]
-    failed: dict[str, list[list[int]]] = {}
-    cus = []
-    for k, c in sorted(seen.items()):
-        if not c["kinds"]:
-            continue
-        kinds = [n for n in order if n in c["kinds"]]
-        cus.append({"xcc": k[0], "cu_key": k[1], "kinds": kinds, "waves": c["waves"], "bad_slot": c["slot"],
-                    "bad_wave": c["thread"] >> 6 if c["thread"] >= 0 else -1,
-                    "bad_lane": c["thread"] & 63 if c["thread"] >= 0 else -1})
-        for n in kinds:
-            failed.setdefault(n, []).append([k[0], k[1]])
-    return {"cus_seen": len(seen), "cus_expected": n_expected, "failed": failed, "cus": cus,
-            "uncovered": [list(k) for k in uncovered], "cus_uncovered": n_uncovered,
-            "approx_hash": majority,
-            "simds_seen_min": min((bin(c["simds"]).count("1") for c in seen.values()), default=0)}
+    by_cu = _by_cu(records)
+    failures = []
+    for k, visits in sorted(by_cu.items()):
+        found, waves, slot, thread = set(), 0, -1, -1
+        for fail, _simds, gbits, s, t, ahash in visits:
+            if fail >> 16 or gbits >> n_exact or bool(fail & FAIL_EXACT) != bool(gbits) or bool(fail & FAIL_REGS) != (s >= 0):
+                found.add("record")
+            found.update(groups[i] for i in range(n_exact) if gbits >> i & 1)
+            if fail & FAIL_REGS:
+                found.add("regs")
+                if s >= 0 and (slot < 0 or (s, t) < (slot, thread)):
+                    slot, thread = s, t
+            if fail & (FAIL_BOUND | FAIL_HASH) or ahash != majority:
+                found.add("approx")
+            if ahash != majority and not fail & (FAIL_BOUND | FAIL_HASH):
+                waves |= 0xF
+            waves |= (fail | fail >> 4 | fail >> 8 | fail >> 12) & 0xF
+        if found:
+            kinds = [n for n in groups + ["record"] if n in found]
+            failures.append((k, kinds, {"kinds": kinds, "waves": waves, "bad_slot": slot,
+                                        "bad_wave": thread >> 6 if thread >= 0 else -1,
+                                        "bad_lane": thread & 63 if thread >= 0 else -1}))
+    return dict(_named_failures(by_cu, expected_cus, failures), approx_hash=majority,
+                simds_seen_min=_simds_seen_min(by_cu, 1))
 
 
 def twin_summary() -> dict:

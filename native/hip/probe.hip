@@ -22,6 +22,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <cstring>
@@ -1297,13 +1298,162 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
 
 // ---------------------------------------------------------------------------- deep self-test (host)
 
-struct SweepResult {
+// The names behind the bits of a sweep's selection: the matrix paths, the vector-ALU groups.
+struct NameTable {
+  int count;
+  const char* (*name)(int);
+  const char* noun;
+
+  int index(const std::string& n) const {
+    for (int i = 0; i < count; ++i)
+      if (n == name(i)) return i;
+    throw std::invalid_argument(std::string("unknown ") + noun + " '" + n + "'");
+  }
+  uint32_t bits(const std::vector<std::string>& names) const {
+    uint32_t b = 0;
+    for (const std::string& n : names) b |= 1u << index(n);
+    return b;
+  }
+  std::pair<py::list, py::list> names_and_checked(uint32_t bits) const {   // every name in bit order; those of `bits`
+    py::list all, checked;
+    for (int i = 0; i < count; ++i) {
+      all.append(name(i));
+      if (bits >> i & 1u) checked.append(name(i));
+    }
+    return {all, checked};
+  }
+};
+constexpr NameTable kPathNames{sp::kNumPaths, sp::path_name, "matrix path"};
+constexpr NameTable kValuNames{sv::kNumNames, sv::group_name, "vector-ALU group"};
+
+// Test hook: a device copy of `count` host words of which one at a time is XORed. flip() first
+// puts the word flipped before back as the host has it; the host array is never written. The
+// stream is idle between runs (CuSession::run synchronises), so plain copies are ordered with it.
+class FlippableUpload {
+ public:
+  FlippableUpload(const uint32_t* host, size_t count) : host_(host), dev_(count) {
+    HIP_OK(hipMemcpy(dev_.p, host, count * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  const uint32_t* p() const { return dev_.p; }
+  void flip(std::optional<size_t> at, uint32_t mask) {
+    if (flipped_) write(*flipped_, 0u);
+    flipped_ = at;
+    if (at) write(*at, mask);
+  }
+
+ private:
+  void write(size_t at, uint32_t mask) {
+    const uint32_t w = host_[at] ^ mask;
+    HIP_OK(hipMemcpy(dev_.p + at, &w, 4, hipMemcpyHostToDevice));
+  }
+  const uint32_t* host_;
+  DevBuf<uint32_t> dev_;
+  std::optional<size_t> flipped_;
+};
+
+// corrupt_expected as a session takes it: word `word` of table `table` XORed with `mask`; -1: none.
+// The sweep's tables are 0 (the bf16 chain's tile) and 1 + p (path p's tile); the vector-ALU
+// sweep's are its exact groups.
+struct WordFlip {
+  int table = -1;
+  uint32_t word = 0, mask = 0;
+};
+
+struct CuRun {
   std::vector<uint32_t> words;   // record_words per workgroup
-  int record_words = st::kSweepRecordWords;
-  int blocks = 0;
-  size_t lds_bytes = 0;
+  int record_words = 0, blocks = 0;
   double ms = 0.0;
 };
+
+// What every per-CU check shares: rounds x (enabled CUs) workgroups on a stream masked to `mask`,
+// 0xff-filled records of which every workgroup must write its own, and a first launch outside the
+// timed span. `who` begins the messages. A session derived from this holds its kernel's inputs,
+// which are destroyed before the stream they were used on; `launch(blocks)` is its kernel's launch.
+class CuSession {
+ protected:
+  CuSession(const char* who, int dev, const std::vector<uint32_t>& mask, int rounds, int record_words)
+      : who_(who), stream_(mask), blocks_(grid(who_, dev, mask, rounds)), record_words_(record_words),
+        out_(static_cast<size_t>(blocks_) * record_words) {}
+
+  template <class Launch>
+  void warm_up(Launch&& launch) {   // loads the code object
+    launch(1);
+    HIP_OK(hipStreamSynchronize(stream_.s));
+  }
+
+  template <class Launch>
+  CuRun run(Launch&& launch) {
+    CuRun res;
+    res.blocks = blocks_;
+    res.record_words = record_words_;
+    const size_t words = static_cast<size_t>(blocks_) * record_words_;
+    HIP_OK(hipMemsetAsync(out_.p, 0xff, words * sizeof(uint32_t), stream_.s));
+    HIP_OK(hipEventRecord(ev_.a, stream_.s));
+    launch(blocks_);
+    HIP_OK(hipEventRecord(ev_.b, stream_.s));
+    res.ms = ev_.ms();
+    HIP_OK(hipStreamSynchronize(stream_.s));
+    res.words.resize(words);
+    HIP_OK(hipMemcpy(res.words.data(), out_.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < blocks_; ++b)
+      if (!st::record_written(res.words.data() + static_cast<size_t>(b) * record_words_))
+        throw std::runtime_error(who_ + ": workgroup " + std::to_string(b) + " left no record");
+    return res;
+  }
+
+  hipStream_t stream() const { return stream_.s; }
+  uint32_t* out() const { return out_.p; }
+
+ private:
+  static int grid(const std::string& who, int dev, const std::vector<uint32_t>& mask, int rounds) {
+    if (rounds < 1 || rounds > 64) throw std::invalid_argument(who + ": rounds in 1..64");
+    int cus = 0;
+    if (mask.empty())
+      cus = cu_count(dev);
+    else
+      for (uint32_t w : mask) cus += __builtin_popcount(w);
+    if (cus <= 0 || cus > 4096) throw std::invalid_argument(who + ": the mask enables no CU");
+    return rounds * cus;
+  }
+
+  std::string who_;
+  Stream stream_;
+  Events ev_;
+  int blocks_, record_words_;
+  DevBuf<uint32_t> out_;
+};
+
+// Test hook behind tests/test_gpu_selftest_sensitivity.py and test_gpu_selftest_valu.py: for every
+// flip one run of `session` with `set_flip(flip)` applied. `fields(run, b)` picks N words of record
+// b; per flip the AND of each over all records, then the OR of each: 2N words.
+struct Sensitivity {
+  std::vector<uint32_t> fields;
+  int records = 0;                // per sweep
+  double seconds = 0.0;           // wall time of the loop
+};
+
+template <size_t N, class Session, class Flip, class SetFlip, class Fields>
+Sensitivity sensitivity(Session& session, uint32_t seed, const std::vector<Flip>& flips, SetFlip&& set_flip, Fields&& fields) {
+  Sensitivity out;
+  out.fields.reserve(flips.size() * 2 * N);
+  const Clock::time_point t0 = Clock::now();
+  for (const Flip& f : flips) {
+    set_flip(f);
+    const CuRun r = session.run(seed, {});
+    out.records = r.blocks;
+    std::array<uint32_t, N> a, o;
+    a.fill(~0u);
+    o.fill(0u);
+    for (int b = 0; b < r.blocks; ++b) {
+      const std::array<uint32_t, N> v = fields(r, b);
+      for (size_t i = 0; i < N; ++i) a[i] &= v[i], o[i] |= v[i];
+    }
+    out.fields.insert(out.fields.end(), a.begin(), a.end());
+    out.fields.insert(out.fields.end(), o.begin(), o.end());
+  }
+  out.seconds = std::chrono::duration<double>(Clock::now() - t0).count();
+  return out;
+}
 
 const std::vector<uint32_t>& path_tiles() {   // independent of seed and device: computed once
   static const std::vector<uint32_t> tiles = [] {
@@ -1317,14 +1467,6 @@ const std::vector<uint32_t>& path_tiles() {   // independent of seed and device:
   }();
   return tiles;
 }
-
-// Test hook: one word of the expected data, XORed on its way to the device. `tile` is -1 (none),
-// 0 (the bf16 chain's tile) or 1 + p (path p's tile). The word goes into the session's own
-// upload; the cached path_tiles() are never written.
-struct ExpectedFlip {
-  int tile = -1;
-  uint32_t word = 0, mask = 0;
-};
 
 using SweepKernel = void (*)(const float*, uint32_t*, uint32_t, SweepInject, uint32_t, uint32_t, const uint32_t*);
 constexpr SweepKernel kSweepKernels[2][2] = {   // [kPaths][kFull]
@@ -1340,27 +1482,17 @@ bool sweep_block_fits(SweepKernel kernel, size_t dynamic_lds) {
   return fit >= 1;
 }
 
-// rounds x (enabled CUs) sweep workgroups on a stream masked to `mask`. Whether one block may
-// hold the whole LDS is asked of the occupancy API, never found out by a failing launch.
-// `paths` != 0 launches the kPaths instantiations instead (same grid, block and LDS), with
-// every path's expected tile uploaded once, and returns their 7-word records. `lds_bytes`
-// (test hook) takes the dynamic-LDS instantiation with that much LDS whatever the device allows.
-// The session holds the buffers, the stream and the kernel choice, made once; `run` launches
-// and reads back. cu_sweep is one session and one run, sweep_sensitivity a run per word.
-class SweepSession {
+// The CuSession of cu_sweep_kernel. Whether one block may hold the whole LDS is asked of the
+// occupancy API, never found out by a failing launch. `paths` != 0 launches the kPaths
+// instantiations instead (same grid, block and LDS), with every path's expected tile uploaded
+// once, and returns their 7-word records. `lds_bytes` (test hook) takes the dynamic-LDS
+// instantiation with that much LDS whatever the device allows. cu_sweep is one session and one
+// run, sweep_sensitivity a run per word.
+class SweepSession : public CuSession {
  public:
   SweepSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t paths,
                std::optional<size_t> lds_bytes = std::nullopt)
-      : paths_(paths), stream_(mask) {
-    if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep: rounds in 1..64");
-    int cus = 0;
-    if (mask.empty())
-      cus = cu_count(dev);
-    else
-      for (uint32_t w : mask) cus += __builtin_popcount(w);
-    if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep: the mask enables no CU");
-    blocks_ = rounds * cus;
-
+      : CuSession("cu_sweep", dev, mask, rounds, paths ? sp::kPathRecordWords : st::kSweepRecordWords), paths_(paths) {
     if (paths & ~sp::kAllPaths) throw std::invalid_argument("cu_sweep_paths: unknown path bit");
     const uint32_t n_min = paths ? static_cast<uint32_t>(sp::kNumPaths * sp::kTileWords) : 4u;   // staging | reduction
     if (lds_bytes && (*lds_bytes % 16 != 0 || *lds_bytes > 65536 || *lds_bytes < n_min * 4u))
@@ -1382,147 +1514,53 @@ class SweepSession {
 
     std::vector<int32_t> tile(32 * 32);
     st::sweep_expected(tile.data());
-    expected_host_.assign(tile.begin(), tile.end());
-    expected_.reset(new DevBuf<float>(expected_host_.size()));
-    HIP_OK(hipMemcpy(expected_->p, expected_host_.data(), expected_host_.size() * sizeof(float), hipMemcpyHostToDevice));
-    record_words_ = paths ? sp::kPathRecordWords : st::kSweepRecordWords;
-    out_.reset(new DevBuf<uint32_t>(static_cast<size_t>(blocks_) * record_words_));
-    if (paths) {
-      tiles_.reset(new DevBuf<uint32_t>(path_tiles().size()));
-      HIP_OK(hipMemcpy(tiles_->p, path_tiles().data(), path_tiles().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    expected_host_.resize(tile.size());
+    for (size_t i = 0; i < tile.size(); ++i) {   // the kernel reads floats: their words
+      const float f = static_cast<float>(tile[i]);
+      std::memcpy(&expected_host_[i], &f, 4);
     }
-    launch(1, 0u, SweepInject{});   // loads the code object outside the timed span
+    expected_.emplace(expected_host_.data(), expected_host_.size());
+    if (paths) tiles_.emplace(path_tiles().data(), path_tiles().size());
+    warm_up([this](int blocks) { launch(blocks, 0u, SweepInject{}); });
   }
 
-  // Puts the device's expected data back as the host computed it, then XORs `f`'s word. The
-  // stream is idle between runs (run() synchronises), so plain copies are ordered with it.
-  void set_flip(const ExpectedFlip& f) {
-    if (flip_.tile >= 0) write_word(flip_, 0u);
-    flip_ = ExpectedFlip{};
-    if (f.tile < 0) return;
-    if (f.tile > sp::kNumPaths) throw std::invalid_argument("corrupt_expected: unknown tile");
-    if (f.tile > 0 && !(paths_ >> (f.tile - 1) & 1u))
-      throw std::invalid_argument(std::string("corrupt_expected: path ") + sp::path_name(f.tile - 1) + " is not selected");
-    const uint32_t words = f.tile == 0 ? 32u * 32u : static_cast<uint32_t>(sp::path_tile_words(f.tile - 1));
+  void set_flip(const WordFlip& f) {
+    expected_->flip(std::nullopt, 0u);   // both uploads clean before the checks: a refused flip leaves none behind
+    if (tiles_) tiles_->flip(std::nullopt, 0u);
+    if (f.table < 0) return;
+    if (f.table > sp::kNumPaths) throw std::invalid_argument("corrupt_expected: unknown tile");
+    if (f.table > 0 && !(paths_ >> (f.table - 1) & 1u))
+      throw std::invalid_argument(std::string("corrupt_expected: path ") + sp::path_name(f.table - 1) + " is not selected");
+    const uint32_t words = f.table == 0 ? 32u * 32u : static_cast<uint32_t>(sp::path_tile_words(f.table - 1));
     if (f.word >= words) throw std::invalid_argument("corrupt_expected: word beyond the tile");
-    write_word(f, f.mask);
-    flip_ = f;
+    if (f.table == 0)
+      expected_->flip(f.word, f.mask);
+    else
+      tiles_->flip(static_cast<size_t>(f.table - 1) * sp::kTileWords + f.word, f.mask);
   }
 
-  SweepResult run(uint32_t seed, SweepInject inj) {
+  CuRun run(uint32_t seed, SweepInject inj) {
     if (inj.kind == kInjectLds && inj.lds_off >= n_) throw std::invalid_argument("cu_sweep: inject offset beyond the LDS array");
-    SweepResult res;
-    res.blocks = blocks_;
-    res.lds_bytes = static_cast<size_t>(n_) * 4;
-    res.record_words = record_words_;
-    const size_t words = static_cast<size_t>(blocks_) * record_words_;
-    HIP_OK(hipMemsetAsync(out_->p, 0xff, words * sizeof(uint32_t), stream_.s));
-    HIP_OK(hipEventRecord(ev_.a, stream_.s));
-    launch(blocks_, seed, inj);
-    HIP_OK(hipEventRecord(ev_.b, stream_.s));
-    res.ms = ev_.ms();
-    HIP_OK(hipStreamSynchronize(stream_.s));
-    res.words.resize(words);
-    HIP_OK(hipMemcpy(res.words.data(), out_->p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int b = 0; b < blocks_; ++b)
-      if (!st::decode_record(res.words.data(), b, record_words_).written())
-        throw std::runtime_error("cu_sweep: workgroup " + std::to_string(b) + " left no record");
-    return res;
+    return CuSession::run([&](int blocks) { launch(blocks, seed, inj); });
   }
+
+  size_t lds_bytes() const { return static_cast<size_t>(n_) * 4; }
 
  private:
-  void write_word(const ExpectedFlip& f, uint32_t mask) {
-    uint32_t w;
-    if (f.tile == 0) {
-      std::memcpy(&w, &expected_host_[f.word], 4);
-      w ^= mask;
-      HIP_OK(hipMemcpy(reinterpret_cast<uint32_t*>(expected_->p) + f.word, &w, 4, hipMemcpyHostToDevice));
-    } else {
-      const size_t at = static_cast<size_t>(f.tile - 1) * sp::kTileWords + f.word;
-      w = path_tiles()[at] ^ mask;
-      HIP_OK(hipMemcpy(tiles_->p + at, &w, 4, hipMemcpyHostToDevice));
-    }
-  }
-
   void launch(int blocks, uint32_t seed, SweepInject j) {
-    hipLaunchKernelGGL(kernel_, dim3(blocks), dim3(kSweepBlock), dynamic_lds_, stream_.s, expected_->p, out_->p, seed, j,
-                       n_, paths_, tiles_ ? tiles_->p : nullptr);
+    hipLaunchKernelGGL(kernel_, dim3(blocks), dim3(kSweepBlock), dynamic_lds_, stream(), reinterpret_cast<const float*>(expected_->p()),
+                       out(), seed, j, n_, paths_, tiles_ ? tiles_->p() : nullptr);
     HIP_OK(hipGetLastError());
   }
 
   uint32_t paths_;
-  Stream stream_;
-  Events ev_;
-  int blocks_ = 0, record_words_ = st::kSweepRecordWords;
   SweepKernel kernel_ = nullptr;
   uint32_t n_ = kLdsDwordsFull, dynamic_lds_ = 0;   // dwords the LDS test covers; bytes of them the launch asks for
-  ExpectedFlip flip_;
-  std::vector<float> expected_host_;
-  std::unique_ptr<DevBuf<float>> expected_;
-  std::unique_ptr<DevBuf<uint32_t>> out_, tiles_;   // tiles_: the path sweep only
+  std::vector<uint32_t> expected_host_;
+  std::optional<FlippableUpload> expected_, tiles_;   // tiles_: the path sweep only
 };
-
-SweepResult cu_sweep(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, SweepInject inj,
-                     uint32_t paths, ExpectedFlip flip, std::optional<size_t> lds_bytes) {
-  HIP_OK(hipSetDevice(dev));
-  SweepSession session(dev, mask, rounds, paths, lds_bytes);
-  session.set_flip(flip);
-  return session.run(seed, inj);
-}
-
-// Test hook behind tests/test_gpu_selftest_sensitivity.py: for every (word, xor mask) of tile
-// `tile` (ExpectedFlip's numbering) one sweep of `rounds` rounds with that word of the expected
-// data corrupted, on one session. Per word the AND and the OR over all records of the fields
-// fail, lds_bad, path_fail and path_waves (the last two 0 when `paths` is 0): 8 words, AND first.
-struct Sensitivity {
-  std::vector<uint32_t> fields;   // 8 per word
-  int records = 0;                // per sweep
-  double seconds = 0.0;           // wall time of the loop
-};
-
-Sensitivity sweep_sensitivity(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, uint32_t paths,
-                              int tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips) {
-  HIP_OK(hipSetDevice(dev));
-  if (flips.size() > 4096) throw std::invalid_argument("sweep_sensitivity: at most 4096 words a call");
-  SweepSession session(dev, mask, rounds, paths);
-  Sensitivity out;
-  out.fields.reserve(flips.size() * 8);
-  const Clock::time_point t0 = Clock::now();
-  for (const auto& f : flips) {
-    session.set_flip(ExpectedFlip{tile, f.first, f.second});
-    const SweepResult r = session.run(seed, SweepInject{});
-    out.records = r.blocks;
-    uint32_t a[4] = {~0u, ~0u, ~0u, ~0u}, o[4] = {0, 0, 0, 0};
-    for (int b = 0; b < r.blocks; ++b) {
-      const st::SweepRecord rec = st::decode_record(r.words.data(), b, r.record_words);
-      const uint32_t v[4] = {rec.fail, rec.lds_bad, rec.path_fail, rec.path_waves};
-      for (int i = 0; i < 4; ++i) a[i] &= v[i], o[i] |= v[i];
-    }
-    out.fields.insert(out.fields.end(), a, a + 4);
-    out.fields.insert(out.fields.end(), o, o + 4);
-  }
-  out.seconds = std::chrono::duration<double>(Clock::now() - t0).count();
-  return out;
-}
 
 // ---- vector-ALU sweep (host) ----
-struct ValuResult {
-  std::vector<uint32_t> words;   // sv::kValuRecordWords per workgroup
-  int blocks = 0;
-  double ms = 0.0;
-};
-
-int valu_group_index(const std::string& name) {
-  for (int g = 0; g < sv::kNumNames; ++g)
-    if (name == sv::group_name(g)) return g;
-  throw std::invalid_argument("unknown vector-ALU group '" + name + "'");
-}
-
-uint32_t valu_group_bits(const std::vector<std::string>& names) {
-  uint32_t bits = 0;
-  for (const std::string& n : names) bits |= 1u << valu_group_index(n);
-  return bits;
-}
 
 const std::vector<uint32_t>& valu_table() {   // the expected words, then the approx ranges: computed once
   static const std::vector<uint32_t> table = [] {
@@ -1534,21 +1572,13 @@ const std::vector<uint32_t>& valu_table() {   // the expected words, then the ap
   return table;
 }
 
-// cu_sweep's session for cu_valu_kernel: the same grid (rounds x enabled CUs), masked stream,
-// 0xff-filled records and launch outside the timed span. The kernel's attributes are read once:
-// a register test that spills to scratch would test memory, so `regs` is refused then.
-class ValuSession {
+// The CuSession of cu_valu_kernel. The kernel's attributes are read once: a register test that
+// spills to scratch would test memory, so `regs` is refused then.
+class ValuSession : public CuSession {
  public:
-  ValuSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t groups) : groups_(groups), stream_(mask) {
-    if (rounds < 1 || rounds > 64) throw std::invalid_argument("cu_sweep_valu: rounds in 1..64");
+  ValuSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t groups)
+      : CuSession("cu_sweep_valu", dev, mask, rounds, sv::kValuRecordWords), groups_(groups) {
     if (!groups || (groups & ~sv::kAllGroups)) throw std::invalid_argument("cu_sweep_valu: no group, or an unknown one");
-    int cus = 0;
-    if (mask.empty())
-      cus = cu_count(dev);
-    else
-      for (uint32_t w : mask) cus += __builtin_popcount(w);
-    if (cus <= 0 || cus > 4096) throw std::invalid_argument("cu_sweep_valu: the mask enables no CU");
-    blocks_ = rounds * cus;
     hipFuncAttributes attr;
     HIP_OK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(cu_valu_kernel)));
     scratch_bytes_ = attr.localSizeBytes;
@@ -1556,64 +1586,36 @@ class ValuSession {
     if ((groups >> sv::kRegs & 1u) && scratch_bytes_ != 0)
       throw std::runtime_error("cu_sweep_valu: the register-file test was compiled with " + std::to_string(scratch_bytes_) +
                                " bytes of scratch a lane, so it would test memory, not registers: 'regs' is refused");
-    table_.reset(new DevBuf<uint32_t>(valu_table().size()));
-    HIP_OK(hipMemcpy(table_->p, valu_table().data(), valu_table().size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    out_.reset(new DevBuf<uint32_t>(static_cast<size_t>(blocks_) * sv::kValuRecordWords));
-    launch(1, 0u, ValuInject{});   // loads the code object outside the timed span
-    HIP_OK(hipStreamSynchronize(stream_.s));
+    table_.emplace(valu_table().data(), valu_table().size());
+    warm_up([this](int blocks) { launch(blocks, 0u, ValuInject{}); });
   }
 
-  // One word of group `group`'s expected words XORed in this session's upload; the cached table is never written.
-  void set_flip(int group, uint32_t word, uint32_t mask) {
-    if (flip_at_ >= 0) write_word(static_cast<size_t>(flip_at_), 0u);
-    flip_at_ = -1;
-    if (group < 0) return;
-    if (group >= sv::kNumExact) throw std::invalid_argument("corrupt_expected: an exact group's name");
-    if (!(groups_ >> group & 1u)) throw std::invalid_argument(std::string("corrupt_expected: group ") + sv::group_name(group) + " is not selected");
-    if (word >= static_cast<uint32_t>(sv::kGroupWords)) throw std::invalid_argument("corrupt_expected: word beyond the group's table");
-    const size_t at = static_cast<size_t>(group) * sv::kGroupWords + word;
-    write_word(at, mask);
-    flip_at_ = static_cast<long long>(at);
+  void set_flip(const WordFlip& f) {
+    table_->flip(std::nullopt, 0u);
+    if (f.table < 0) return;
+    if (f.table >= sv::kNumExact) throw std::invalid_argument("corrupt_expected: an exact group's name");
+    if (!(groups_ >> f.table & 1u)) throw std::invalid_argument(std::string("corrupt_expected: group ") + sv::group_name(f.table) + " is not selected");
+    if (f.word >= static_cast<uint32_t>(sv::kGroupWords)) throw std::invalid_argument("corrupt_expected: word beyond the group's table");
+    table_->flip(static_cast<size_t>(f.table) * sv::kGroupWords + f.word, f.mask);
   }
 
-  ValuResult run(uint32_t seed, ValuInject inj) {
-    ValuResult res;
-    res.blocks = blocks_;
-    const size_t words = static_cast<size_t>(blocks_) * sv::kValuRecordWords;
-    HIP_OK(hipMemsetAsync(out_->p, 0xff, words * sizeof(uint32_t), stream_.s));
-    HIP_OK(hipEventRecord(ev_.a, stream_.s));
-    launch(blocks_, seed, inj);
-    HIP_OK(hipEventRecord(ev_.b, stream_.s));
-    res.ms = ev_.ms();
-    HIP_OK(hipStreamSynchronize(stream_.s));
-    res.words.resize(words);
-    HIP_OK(hipMemcpy(res.words.data(), out_->p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int b = 0; b < blocks_; ++b)
-      if (!sv::decode_valu_record(res.words.data(), b).written())
-        throw std::runtime_error("cu_sweep_valu: workgroup " + std::to_string(b) + " left no record");
-    return res;
+  CuRun run(uint32_t seed, ValuInject inj) {
+    return CuSession::run([&](int blocks) { launch(blocks, seed, inj); });
   }
 
   size_t scratch_bytes() const { return scratch_bytes_; }
   int regs_per_lane() const { return regs_per_lane_; }
 
  private:
-  void write_word(size_t at, uint32_t mask) {
-    const uint32_t w = valu_table()[at] ^ mask;
-    HIP_OK(hipMemcpy(table_->p + at, &w, 4, hipMemcpyHostToDevice));
-  }
   void launch(int blocks, uint32_t seed, ValuInject j) {
-    hipLaunchKernelGGL(cu_valu_kernel, dim3(blocks), dim3(kSweepBlock), 0, stream_.s, table_->p, out_->p, seed, j, groups_);
+    hipLaunchKernelGGL(cu_valu_kernel, dim3(blocks), dim3(kSweepBlock), 0, stream(), table_->p(), out(), seed, j, groups_);
     HIP_OK(hipGetLastError());
   }
 
   uint32_t groups_;
-  Stream stream_;
-  Events ev_;
-  int blocks_ = 0, regs_per_lane_ = 0;
+  int regs_per_lane_ = 0;
   size_t scratch_bytes_ = 0;
-  long long flip_at_ = -1;
-  std::unique_ptr<DevBuf<uint32_t>> table_, out_;
+  std::optional<FlippableUpload> table_;
 };
 
 using LanesKernel = void (*)(uint32_t*);
@@ -1647,7 +1649,7 @@ ValuInject parse_valu_inject(const py::object& inject) {
   const std::string kind = t[2].cast<std::string>();
   if (kind == "valu" && t.size() == 4) {
     inj.kind = kValuInjectGroup;
-    inj.arg = valu_group_index(t[3].cast<std::string>());
+    inj.arg = kValuNames.index(t[3].cast<std::string>());
     if (inj.arg >= sv::kNumExact) throw std::invalid_argument("cu_sweep_valu: inject 'valu' names an exact group");
   } else if (kind == "regs" && t.size() == 4) {
     inj.kind = kValuInjectRegs;
@@ -1775,12 +1777,6 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   return res;
 }
 
-int path_index(const std::string& name) {
-  for (int p = 0; p < sp::kNumPaths; ++p)
-    if (name == sp::path_name(p)) return p;
-  throw std::invalid_argument("unknown matrix path '" + name + "'");
-}
-
 using TileKernel = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t*);
 
 // matrix_tile_kernel<P, opsel / 4, opsel % 4> for every opsel of the sequence: the byte selects
@@ -1870,7 +1866,7 @@ SweepInject parse_inject(const py::object& inject, bool paths) {
   const std::string kind = t[2].cast<std::string>();
   if (paths) {
     inj.kind = kInjectPath;
-    inj.path = path_index(kind);
+    inj.path = kPathNames.index(kind);
   } else if (kind == "mfma") {
     inj.kind = kInjectMfma;
   } else if (kind == "lds") {
@@ -1882,63 +1878,153 @@ SweepInject parse_inject(const py::object& inject, bool paths) {
   return inj;
 }
 
-// "bf16" is tile 0, path p's tile 1 + p (ExpectedFlip).
-int tile_index(const std::string& name) { return name == "bf16" ? 0 : 1 + path_index(name); }
+// "bf16" is table 0, path p's tile 1 + p (WordFlip).
+int tile_index(const std::string& name) { return name == "bf16" ? 0 : 1 + kPathNames.index(name); }
+int group_index(const std::string& name) { return kValuNames.index(name); }
 
-// corrupt_expected of cu_sweep: (word, xor); of cu_sweep_paths: (tile name, word, xor).
-ExpectedFlip parse_flip(const py::object& corrupt, bool named) {
-  ExpectedFlip f;
+// corrupt_expected = (table name, word, xor), or (word, xor) of table 0 where `table` is null. `usage` is the message.
+WordFlip parse_flip(const py::object& corrupt, int (*table)(const std::string&), const char* usage) {
+  WordFlip f;
   if (corrupt.is_none()) return f;
   const py::tuple t = corrupt.cast<py::tuple>();
-  if (t.size() != (named ? 3u : 2u))
-    throw std::invalid_argument(named ? "cu_sweep_paths: corrupt_expected = ('bf16' | path name, word, xor)"
-                                      : "cu_sweep: corrupt_expected = (word, xor)");
-  f.tile = named ? tile_index(t[0].cast<std::string>()) : 0;
-  f.word = t[named ? 1 : 0].cast<uint32_t>();
-  f.mask = t[named ? 2 : 1].cast<uint32_t>();
+  const size_t named = table ? 1 : 0;
+  if (t.size() != 2 + named) throw std::invalid_argument(usage);
+  f.table = table ? table(t[0].cast<std::string>()) : 0;
+  f.word = t[named].cast<uint32_t>();
+  f.mask = t[named + 1].cast<uint32_t>();
   return f;
 }
 
-uint32_t path_bits(const std::vector<std::string>& names) {
-  uint32_t bits = 0;
-  for (const std::string& name : names) bits |= 1u << path_index(name);
-  return bits;
+static_assert(st::kNoBadOffset == sv::kNoBad, "one 'none' word in every record");
+int64_t or_minus1(uint32_t v) { return v == sv::kNoBad ? int64_t(-1) : int64_t(v); }
+
+// {words: [(AND tuple, OR tuple)] per flip, records, seconds}; `tuple` packs one half's n words.
+template <class Tuple>
+py::dict sensitivity_dict(const Sensitivity& r, size_t flips, size_t n, Tuple&& tuple) {
+  py::list words;
+  for (size_t i = 0; i < flips; ++i) {
+    const uint32_t* f = r.fields.data() + 2 * n * i;
+    words.append(py::make_tuple(tuple(f), tuple(f + n)));
+  }
+  py::dict d;
+  d["words"] = words;
+  d["records"] = r.records;
+  d["seconds"] = r.seconds;
+  return d;
 }
 
 // cu_sweep (`paths` null: 5-field records) and cu_sweep_paths (7 fields, and the keys `paths` / `checked`).
 py::dict sweep_binding(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed,
                        const std::vector<std::string>* paths, const py::object& inject, const py::object& corrupt_expected,
                        std::optional<size_t> lds_bytes) {
-  const uint32_t bits = paths ? path_bits(*paths) : 0u;
+  const uint32_t bits = paths ? kPathNames.bits(*paths) : 0u;
   if (paths && !bits) throw std::invalid_argument("cu_sweep_paths: no path selected");
   const SweepInject inj = parse_inject(inject, paths != nullptr);
-  const ExpectedFlip flip = parse_flip(corrupt_expected, paths != nullptr);
-  SweepResult r;
+  const WordFlip flip = paths ? parse_flip(corrupt_expected, tile_index, "cu_sweep_paths: corrupt_expected = ('bf16' | path name, word, xor)")
+                              : parse_flip(corrupt_expected, nullptr, "cu_sweep: corrupt_expected = (word, xor)");
+  CuRun r;
+  size_t lds = 0;
   {
     py::gil_scoped_release nogil;
-    r = cu_sweep(dev, mask, rounds, seed, inj, bits, flip, lds_bytes);
+    HIP_OK(hipSetDevice(dev));
+    SweepSession session(dev, mask, rounds, bits, lds_bytes);
+    session.set_flip(flip);
+    r = session.run(seed, inj);
+    lds = session.lds_bytes();
   }
   py::list recs;
   for (int b = 0; b < r.blocks; ++b) {
     const st::SweepRecord rec = st::decode_record(r.words.data(), b, r.record_words);
-    const py::tuple base = py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds,
-                                          rec.lds_bad == st::kNoBadOffset ? int64_t(-1) : int64_t(rec.lds_bad));
+    const py::tuple base = py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds, or_minus1(rec.lds_bad));
     recs.append(paths ? py::tuple(base + py::make_tuple(rec.path_fail, rec.path_waves)) : base);
   }
   py::dict d;
   d["records"] = recs;
   if (paths) {
-    py::list names, checked;
-    for (int p = 0; p < sp::kNumPaths; ++p) {
-      names.append(sp::path_name(p));
-      if (bits >> p & 1u) checked.append(sp::path_name(p));
-    }
+    const auto [names, checked] = kPathNames.names_and_checked(bits);
     d["paths"] = names;
     d["checked"] = checked;
   }
-  d["lds_bytes"] = r.lds_bytes;
+  d["lds_bytes"] = lds;
   d["ms"] = r.ms;
   return d;
+}
+
+py::dict valu_binding(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& groups,
+                      const py::object& inject, const py::object& corrupt_expected) {
+  const uint32_t bits = kValuNames.bits(groups);
+  const ValuInject inj = parse_valu_inject(inject);
+  const WordFlip flip = parse_flip(corrupt_expected, group_index, "cu_sweep_valu: corrupt_expected = (group, word, xor)");
+  CuRun r;
+  size_t scratch = 0;
+  int regs = 0;
+  {
+    py::gil_scoped_release nogil;
+    HIP_OK(hipSetDevice(dev));
+    ValuSession session(dev, mask, rounds, bits);
+    session.set_flip(flip);
+    r = session.run(seed, inj);
+    scratch = session.scratch_bytes();
+    regs = session.regs_per_lane();
+  }
+  py::list recs;
+  for (int b = 0; b < r.blocks; ++b) {
+    const sv::ValuRecord rec = sv::decode_valu_record(r.words.data(), b);
+    recs.append(py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds, rec.groups, or_minus1(rec.bad_slot), or_minus1(rec.bad_thread),
+                               rec.approx_hash));
+  }
+  py::dict d;
+  d["records"] = recs;
+  const auto [names, checked] = kValuNames.names_and_checked(bits);
+  d["groups"] = names;
+  d["checked"] = checked;
+  d["reg_slots"] = sv::kRegSlots;
+  d["regs_per_lane"] = regs;
+  d["scratch_bytes"] = scratch;
+  d["ms"] = r.ms;
+  return d;
+}
+
+// Per word the fields fail, lds_bad, path_fail and path_waves (the last two 0 when `paths` is empty).
+py::dict sweep_sensitivity(int dev, const std::string& tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
+                           const std::vector<std::string>& paths, const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
+  const uint32_t bits = kPathNames.bits(paths);
+  const int t = tile_index(tile);
+  Sensitivity r;
+  {
+    py::gil_scoped_release nogil;
+    HIP_OK(hipSetDevice(dev));
+    if (flips.size() > 4096) throw std::invalid_argument("sweep_sensitivity: at most 4096 words a call");
+    SweepSession session(dev, mask, rounds, bits);
+    r = sensitivity<4>(
+        session, seed, flips,
+        [&](const std::pair<uint32_t, uint32_t>& f) { session.set_flip(WordFlip{t, f.first, f.second}); },
+        [](const CuRun& run, int b) {
+          const st::SweepRecord rec = st::decode_record(run.words.data(), b, run.record_words);
+          return std::array<uint32_t, 4>{rec.fail, rec.lds_bad, rec.path_fail, rec.path_waves};
+        });
+  }
+  return sensitivity_dict(r, flips.size(), 4, [](const uint32_t* f) { return py::make_tuple(f[0], or_minus1(f[1]), f[2], f[3]); });
+}
+
+py::dict valu_sensitivity(int dev, const std::string& group, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
+                          const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
+  const int g = kValuNames.index(group);
+  if (flips.size() > 4096) throw std::invalid_argument("valu_sensitivity: at most 4096 words a call");
+  Sensitivity r;
+  {
+    py::gil_scoped_release nogil;
+    HIP_OK(hipSetDevice(dev));
+    ValuSession session(dev, mask, rounds, sv::kAllExact);
+    r = sensitivity<2>(
+        session, seed, flips,
+        [&](const std::pair<uint32_t, uint32_t>& f) { session.set_flip(WordFlip{g, f.first, f.second}); },
+        [](const CuRun& run, int b) {
+          const sv::ValuRecord rec = sv::decode_valu_record(run.words.data(), b);
+          return std::array<uint32_t, 2>{rec.fail, rec.groups};
+        });
+  }
+  return sensitivity_dict(r, flips.size(), 2, [](const uint32_t* f) { return py::make_tuple(f[0], f[1]); });
 }
 
 }  // namespace
@@ -2032,7 +2118,7 @@ PYBIND11_MODULE(_probe, m) {
       "matrix_tile",
       [](const std::string& path, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b,
          const std::vector<uint32_t>& scale_a, const std::vector<uint32_t>& scale_b, std::pair<int, int> opsel) {
-        const int p = path_index(path);
+        const int p = kPathNames.index(path);
         const std::vector<uint32_t> w = matrix_tile(p, a, b, scale_a, scale_b, opsel.first, opsel.second);
         py::list c;
         const size_t n = static_cast<size_t>(sp::path_dim(p)) * sp::path_dim(p);
@@ -2076,27 +2162,7 @@ PYBIND11_MODULE(_probe, m) {
       "lds_bytes as in cu_sweep, 36864 (the nine staged tiles)..65536; a visit of every CU is not promised then.");
   m.def(
       "sweep_sensitivity",
-      [](int dev, const std::string& tile, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
-         const std::vector<std::string>& paths, const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
-        const uint32_t bits = path_bits(paths);
-        const int t = tile_index(tile);
-        Sensitivity r;
-        {
-          py::gil_scoped_release nogil;
-          r = sweep_sensitivity(dev, mask, rounds, seed, bits, t, flips);
-        }
-        py::list words;
-        for (size_t i = 0; i < flips.size(); ++i) {
-          const uint32_t* f = r.fields.data() + 8 * i;
-          auto off = [](uint32_t v) { return v == st::kNoBadOffset ? int64_t(-1) : int64_t(v); };
-          words.append(py::make_tuple(py::make_tuple(f[0], off(f[1]), f[2], f[3]), py::make_tuple(f[4], off(f[5]), f[6], f[7])));
-        }
-        py::dict d;
-        d["words"] = words;
-        d["records"] = r.records;
-        d["seconds"] = r.seconds;
-        return d;
-      },
+      &sweep_sensitivity,
       py::arg("device"), py::arg("tile"), py::arg("flips"), py::arg("paths") = std::vector<std::string>{},
       py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 1, py::arg("seed") = 0x5eed5eedu,
       "Test hook: for every (word, xor) of `flips` one sweep (cu_sweep_paths over `paths`, or cu_sweep when "
@@ -2146,53 +2212,7 @@ PYBIND11_MODULE(_probe, m) {
       "every CU. Raises MemoryError when the buffer cannot be allocated.");
   m.def(
       "cu_sweep_valu",
-      [](int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& groups,
-         const py::object& inject, const py::object& corrupt_expected) {
-        const uint32_t bits = valu_group_bits(groups);
-        const ValuInject inj = parse_valu_inject(inject);
-        int fg = -1;
-        uint32_t fw = 0, fm = 0;
-        if (!corrupt_expected.is_none()) {
-          const py::tuple t = corrupt_expected.cast<py::tuple>();
-          if (t.size() != 3) throw std::invalid_argument("cu_sweep_valu: corrupt_expected = (group, word, xor)");
-          fg = valu_group_index(t[0].cast<std::string>());
-          fw = t[1].cast<uint32_t>();
-          fm = t[2].cast<uint32_t>();
-        }
-        ValuResult r;
-        size_t scratch = 0;
-        int regs = 0;
-        {
-          py::gil_scoped_release nogil;
-          HIP_OK(hipSetDevice(dev));
-          ValuSession session(dev, mask, rounds, bits);
-          session.set_flip(fg, fw, fm);
-          r = session.run(seed, inj);
-          scratch = session.scratch_bytes();
-          regs = session.regs_per_lane();
-        }
-        py::list recs;
-        for (int b = 0; b < r.blocks; ++b) {
-          const sv::ValuRecord rec = sv::decode_valu_record(r.words.data(), b);
-          auto opt = [](uint32_t v) { return v == sv::kNoBad ? int64_t(-1) : int64_t(v); };
-          recs.append(py::make_tuple(rec.xcc, rec.hw_id, rec.fail, rec.simds, rec.groups, opt(rec.bad_slot), opt(rec.bad_thread),
-                                     rec.approx_hash));
-        }
-        py::list names, checked;
-        for (int g = 0; g < sv::kNumNames; ++g) {
-          names.append(sv::group_name(g));
-          if (bits >> g & 1u) checked.append(sv::group_name(g));
-        }
-        py::dict d;
-        d["records"] = recs;
-        d["groups"] = names;
-        d["checked"] = checked;
-        d["reg_slots"] = sv::kRegSlots;
-        d["regs_per_lane"] = regs;
-        d["scratch_bytes"] = scratch;
-        d["ms"] = r.ms;
-        return d;
-      },
+      &valu_binding,
       py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
       py::arg("seed") = 0x5eed5eedu, py::arg("groups") = std::vector<std::string>{}, py::arg("inject") = py::none(),
       py::arg("corrupt_expected") = py::none(),
@@ -2211,7 +2231,7 @@ PYBIND11_MODULE(_probe, m) {
   m.def(
       "valu_lanes",
       [](const std::string& group) -> py::object {
-        const int g = valu_group_index(group);
+        const int g = kValuNames.index(group);
         const std::vector<uint32_t> w = valu_lanes(g);
         py::list out;
         for (uint32_t v : w) {
@@ -2225,41 +2245,7 @@ PYBIND11_MODULE(_probe, m) {
       "of exp2, log2, rcp, rsq, sqrt.");
   m.def(
       "valu_sensitivity",
-      [](int dev, const std::string& group, const std::vector<std::pair<uint32_t, uint32_t>>& flips,
-         const std::vector<uint32_t>& mask, int rounds, uint32_t seed) {
-        const int g = valu_group_index(group);
-        if (flips.size() > 4096) throw std::invalid_argument("valu_sensitivity: at most 4096 words a call");
-        std::vector<uint32_t> fields;
-        int records = 0;
-        double seconds = 0.0;
-        {
-          py::gil_scoped_release nogil;
-          HIP_OK(hipSetDevice(dev));
-          ValuSession session(dev, mask, rounds, sv::kAllExact);
-          const Clock::time_point t0 = Clock::now();
-          for (const auto& f : flips) {
-            session.set_flip(g, f.first, f.second);
-            const ValuResult r = session.run(seed, ValuInject{});
-            records = r.blocks;
-            uint32_t a[2] = {~0u, ~0u}, o[2] = {0, 0};
-            for (int b = 0; b < r.blocks; ++b) {
-              const sv::ValuRecord rec = sv::decode_valu_record(r.words.data(), b);
-              a[0] &= rec.fail, a[1] &= rec.groups, o[0] |= rec.fail, o[1] |= rec.groups;
-            }
-            fields.insert(fields.end(), {a[0], a[1], o[0], o[1]});
-          }
-          seconds = std::chrono::duration<double>(Clock::now() - t0).count();
-        }
-        py::list words;
-        for (size_t i = 0; i < flips.size(); ++i)
-          words.append(py::make_tuple(py::make_tuple(fields[4 * i], fields[4 * i + 1]),
-                                      py::make_tuple(fields[4 * i + 2], fields[4 * i + 3])));
-        py::dict d;
-        d["words"] = words;
-        d["records"] = records;
-        d["seconds"] = seconds;
-        return d;
-      },
+      &valu_sensitivity,
       py::arg("device"), py::arg("group"), py::arg("flips"), py::arg("cu_mask") = std::vector<uint32_t>{},
       py::arg("rounds") = 1, py::arg("seed") = 0x5eed5eedu,
       "Test hook: for every (word, xor) of `flips` one cu_sweep_valu over every exact group with that word of `group`'s "

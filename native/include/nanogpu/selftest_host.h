@@ -96,10 +96,14 @@ constexpr uint32_t kRecordUnwritten = 0xffffffffu;   // the host fills the recor
 NANOGPU_HD inline uint32_t hw_cu_key(uint32_t hw_id) { return (hw_id >> 8) & 0xffu; }
 NANOGPU_HD inline uint32_t hw_simd(uint32_t hw_id) { return (hw_id >> 4) & 3u; }
 
+// Every per-CU record (this one, and selftest_valu_host.h's) begins with xcc, hw_id, fail: `w` is a record's first word.
+inline bool record_written(const uint32_t* w) {
+  return !(w[0] == kRecordUnwritten && w[1] == kRecordUnwritten && w[2] == kRecordUnwritten);
+}
+
 // cu_sweep_paths appends two words (selftest_paths_host.h: kPathRecordWords); a 5-word record has them 0.
 struct SweepRecord {
   uint32_t xcc, hw_id, fail, simds, lds_bad, path_fail, path_waves;
-  bool written() const { return !(xcc == kRecordUnwritten && hw_id == kRecordUnwritten && fail == kRecordUnwritten); }
 };
 
 inline SweepRecord decode_record(const uint32_t* words, size_t block, int record_words) {

@@ -347,7 +347,6 @@ constexpr int kFailExactShift = 0, kFailRegsShift = 4, kFailBoundShift = 8, kFai
 
 struct ValuRecord {
   uint32_t xcc, hw_id, fail, simds, groups, bad_slot, bad_thread, approx_hash;
-  bool written() const { return !(xcc == kRecordUnwritten && hw_id == kRecordUnwritten && fail == kRecordUnwritten); }
 };
 
 inline ValuRecord decode_valu_record(const uint32_t* words, size_t block) {

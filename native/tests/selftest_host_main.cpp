@@ -89,7 +89,13 @@ int main() {
                               0xffffffffu};
   const st::SweepRecord r0 = st::decode_record(words, 0, st::kSweepRecordWords),
                         r1 = st::decode_record(words, 1, st::kSweepRecordWords);
-  CHECK(r0.written() && !r1.written());
+  CHECK(st::record_written(words) && !st::record_written(words + st::kSweepRecordWords));
+  for (int i = 0; i < 3; ++i) {   // any one of the three leading words changed: written
+    uint32_t w[3] = {st::kRecordUnwritten, st::kRecordUnwritten, st::kRecordUnwritten};
+    CHECK(!st::record_written(w));
+    w[i] ^= 1u << (7 * i);
+    CHECK(st::record_written(w));
+  }
   CHECK(r0.path_fail == 0 && r0.path_waves == 0);   // a 5-word record has no path words
   CHECK(r0.xcc == 3 && st::hw_cu_key(r0.hw_id) == 0xa5 && st::hw_simd(r0.hw_id) == 3);
   CHECK((r0.fail & st::kFailLds) && (r0.fail & 0xf) == 2 && r0.lds_bad == 40959);

@@ -93,10 +93,10 @@ int main() {
   namespace st = nanogpu::selftest;
   const st::SweepRecord r0 = st::decode_record(words, 0, sp::kPathRecordWords),
                         r1 = st::decode_record(words, 1, sp::kPathRecordWords);
-  CHECK(r0.written() && !r1.written());
+  CHECK(st::record_written(words) && !st::record_written(words + sp::kPathRecordWords) && r1.xcc == st::kRecordUnwritten);
   CHECK(r0.xcc == 3 && r0.path_fail == ((1u << sp::kF16) | (1u << sp::kMxFp4)) && r0.path_waves == 5);
   const st::SweepRecord r5 = st::decode_record(words, 0, st::kSweepRecordWords);   // the same words as a plain record
-  CHECK(r5.written() && r5.xcc == 3 && r5.path_fail == 0 && r5.path_waves == 0);
+  CHECK(r5.xcc == 3 && r5.path_fail == 0 && r5.path_waves == 0);
 
   if (failures) return 1;
   std::puts(json.c_str());

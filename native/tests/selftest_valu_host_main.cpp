@@ -154,7 +154,8 @@ int main() {
   const uint32_t rec[16] = {2, 0x0000a5b0u, 0x0a0, 0xf, 0, 17, 130, 0x12345678u, 0xffffffffu, 0xffffffffu, 0xffffffffu,
                             0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
   const sv::ValuRecord r0 = sv::decode_valu_record(rec, 0), r1 = sv::decode_valu_record(rec, 1);
-  CHECK(r0.written() && !r1.written() && r0.bad_slot == 17 && r0.bad_thread == 130 && r0.approx_hash == 0x12345678u);
+  CHECK(nanogpu::selftest::record_written(rec) && !nanogpu::selftest::record_written(rec + sv::kValuRecordWords));
+  CHECK(r0.xcc == 2 && r1.fail == sv::kNoBad && r0.bad_slot == 17 && r0.bad_thread == 130 && r0.approx_hash == 0x12345678u);
 
   if (failures) return 1;
   std::puts(json.c_str());

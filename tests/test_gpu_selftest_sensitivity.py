@@ -117,6 +117,17 @@ def test_the_python_hook_agrees_with_the_loop_and_a_zero_xor_is_clean(P, name):
     assert [rec for rec in r0["records"] if (rec[2], rec[4], rec[5], rec[6]) != (0, -1, 0, 0)] == []
 
 
+@pytest.mark.parametrize("name", ["bf16", "f16"])
+def test_a_flipped_word_is_restored_before_the_next_flip(P, name):
+    """Both uploads of the sweep's session (the bf16 tile; the path tiles), all paths selected: after
+    word 5 was flipped, a zero XOR of word 6 is clean on every record only if word 5 was put back."""
+    from nanogpu.probe.selftest import PATHS
+
+    r = P.sweep_sensitivity(0, name, [(5, 1 << 5), (6, 0), (6, 1 << 6)], list(PATHS), [], 1, SEED)
+    fails, clean = (expected_fields(name),) * 2, ((0, -1, 0, 0),) * 2
+    assert [tuple(tuple(half) for half in w) for w in r["words"]] == [fails, clean, fails]
+
+
 def test_the_hook_rejects_a_word_beyond_the_tile_and_a_path_not_selected(P):
     from nanogpu.probe.selftest import PATHS
 

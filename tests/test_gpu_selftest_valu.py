@@ -144,6 +144,19 @@ def test_every_word_of_every_table_can_fail_the_sweep(P):
     print(f"sensitivity: {128 * len(EXACT_GROUPS)} sweeps in {time.perf_counter() - t0:.2f} s")
 
 
+def test_a_flipped_word_is_restored_before_the_next_flip(P):
+    """Within one group a word left corrupted would hide behind the next one's failure. A zero XOR of
+    the word flipped before is clean on every record: the XOR starts from the host's word each time, and
+    the host's table was not written. A zero XOR of another word is clean only if the word flipped before
+    was put back; the words around both must still fail."""
+    def words(flips):
+        return [tuple(tuple(half) for half in w) for w in P.valu_sensitivity(0, "fma32", flips)["words"]]
+
+    fails, clean = ((0xF, 1), (0xF, 1)), ((0, 0), (0, 0))
+    assert words([(5, 1 << 3), (5, 0), (6, 1 << 9)]) == [fails, clean, fails]
+    assert words([(5, 1 << 3), (6, 0), (6, 1 << 9)]) == [fails, clean, fails]   # word 5 restored
+
+
 def test_masked_to_one_unit(P):
     from nanogpu.agent import cumask
     from nanogpu.probe.selftest_valu import GROUPS
