@@ -27,6 +27,8 @@ format, joined with what it granted:
     nanogpu_selftest_path_cus_failed{device,path}                    CUs that failed that path
   per device, when the deep self-test also ran the vector-ALU part (--selftest-valu; absent otherwise)
     nanogpu_selftest_valu_checked{device}                            groups the last run checked on every CU
+  per device, when the deep self-test also ran the scalar part (--selftest-scalar; absent otherwise)
+    nanogpu_selftest_scalar_checked{device}                          groups the last run checked on every CU
   per device, only with --selftest-fence (agent/node.py: a failing CU's mask unit is fenced, not the GPU)
     nanogpu_selftest_fenced_cus{device}                              CUs in fenced units
     nanogpu_selftest_fenced_units_in_use{device}                     fenced units a grant from before still holds
@@ -179,6 +181,9 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
         family("nanogpu_selftest_valu_checked", "gauge",
                "vector-ALU groups (with approx and regs) the last deep self-test ran on every CU",
                [(_labels(device=i), len(r["valu"]["checked"])) for i, r in reps if r.get("valu")])
+        family("nanogpu_selftest_scalar_checked", "gauge",
+               "scalar groups (with smem and sregs) the last deep self-test ran on every CU",
+               [(_labels(device=i), len(r["scalar"]["checked"])) for i, r in reps if r.get("scalar")])
     if fence is not None:
         def per_device(key):
             return [(_labels(device=i), v) for i, v in sorted(fence.get(key, {}).items())]

@@ -140,7 +140,7 @@ class NodeAgent:
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
                  selftest_period_s: float = 0.0, selftest_paths=None, selftest_fence: int = 0,
-                 selftest_fence_reset: bool = False, selftest_valu=None):
+                 selftest_fence_reset: bool = False, selftest_valu=None, selftest_scalar=None):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -155,6 +155,7 @@ class NodeAgent:
         self.selftest_hbm_mib = selftest_hbm_mib  # cap of the HBM pattern check (0: free HBM less 2 GiB)
         self.selftest_period_s = selftest_period_s
         from ..probe.selftest import parse_paths
+        from ..probe.selftest_scalar import parse_scalar
         from ..probe.selftest_valu import parse_valu
 
         def part_of_deep(parse, spec) -> list[str]:   # "all", "a,b" or names; any of them makes the sweep deep
@@ -166,6 +167,7 @@ class NodeAgent:
         self.selftest_paths = part_of_deep(parse_paths, selftest_paths)   # matrix paths every deep sweep also runs
         self._no_paths_logged = False
         self.selftest_valu = part_of_deep(parse_valu, selftest_valu)      # vector-ALU groups, 'approx' and 'regs'
+        self.selftest_scalar = part_of_deep(parse_scalar, selftest_scalar)   # scalar groups, 'smem' and 'sregs'
         # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
         # CU-mask units that hold them (at most this many a device) instead of its health (`_deep_fenced`)
         self.selftest_fence = max(0, int(selftest_fence))
@@ -419,7 +421,8 @@ class NodeAgent:
             if self.selftest_fence and self.plugin is not None and self._is_spx(i):
                 r, fenced_now = self._deep_fenced(P, i, bits, nbytes)
             else:
-                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths, valu=self.selftest_valu)
+                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths, valu=self.selftest_valu,
+                                  scalar=self.selftest_scalar)
             reports[i] = r
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
@@ -446,15 +449,15 @@ class NodeAgent:
 
         dc = self.plugin.cus[i]
         paths = self.selftest_paths
-        valu = self.selftest_valu
-        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths, valu=valu)
+        valu, scalar = self.selftest_valu, self.selftest_scalar
+        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths, valu=valu, scalar=scalar)
         if sweep.ok:
-            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths, valu=valu) if nbytes else sweep), False
+            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths, valu=valu, scalar=scalar) if nbytes else sweep), False
         if not fenceable(sweep):
             return sweep, False
         all_bits = bits if bits is not None else list(range(dc.cus))
         units = sorted({b // dc.unit for b in all_bits} - dc.fenced)
-        loc = localise_failure(P, i, sweep, units, dc.unit, paths, valu=valu)
+        loc = localise_failure(P, i, sweep, units, dc.unit, paths, valu=valu, scalar=scalar)
         self.localise_seconds[i] = loc.seconds
         bad = set(loc.bad_units)
         why = (f"CUs {loc.unexplained} failed and no unit swept alone explains them" if loc.unexplained
@@ -466,7 +469,7 @@ class NodeAgent:
             log.warning("agent %s: device %d is not fenced: %s", self.node, i, why)
             return sweep, False
         verify = deep_selftest(P, i, cu_mask_bits=[b for b in all_bits if b // dc.unit not in bad],
-                               hbm_bytes=nbytes, paths=paths, valu=valu)
+                               hbm_bytes=nbytes, paths=paths, valu=valu, scalar=scalar)
         stray = sorted(set(verify.cu_keys) & failed_cus(sweep))
         if verify.ok and stray:
             verify.ok = False
@@ -640,9 +643,10 @@ def build_parser():
                     help="the start-up self-test checks every CU (MFMA pipes, LDS) and the free HBM with an "
                          "address-derived pattern instead of one tile and 16 MiB (implies --selftest)")
     from ..probe.selftest import parse_paths
+    from ..probe.selftest_scalar import parse_scalar
     from ..probe.selftest_valu import parse_valu
 
-    def names_action(parse, noun: str):        # --selftest-paths and --selftest-valu imply --selftest-deep
+    def names_action(parse, noun: str):        # --selftest-paths, --selftest-valu and --selftest-scalar imply --selftest-deep
         class _Names(argparse.Action):
             def __call__(self, parser, ns, values, option_string=None):
                 try:
@@ -664,6 +668,12 @@ def build_parser():
                          "instructions, the transcendentals and a pattern test of the vector register file: 'all' or a "
                          "comma-separated list of fma32, fma64, pkfma16, pkfma32, addmul32, int32, int64, bits, dot, "
                          "cvt, xlane, approx, regs (implies --selftest-deep; start-up and periodic runs alike)")
+    ap.add_argument("--selftest-scalar", action=names_action(parse_scalar, "group"), default=[], metavar="all|LIST",
+                    help="the deep self-test also runs, on all four waves of every CU, exact chains of scalar-ALU "
+                         "instructions, the vector / scalar boundary, scalar loads of every width and a pattern test of the "
+                         "wave's scalar registers: 'all' or a comma-separated list of add, mul, shift, logic, bits, cmp, "
+                         "vcc, smem, sregs (implies --selftest-deep; start-up and periodic runs alike)")
+
     class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
         def __call__(self, parser, ns, values, option_string=None):
             if values < 0:
@@ -717,6 +727,7 @@ def main(argv: list[str] | None = None) -> int:
                           pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
                           selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths, selftest_valu=a.selftest_valu,
+                          selftest_scalar=a.selftest_scalar,
                           selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset)
         await agent.start()
         if a.selftest:

@@ -20,6 +20,10 @@ one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe.hip)
   tiles below are the Python twin of native/include/nanogpu/selftest_paths_host.h, which
   states the exactness argument. `fold_paths` reports per CU which paths failed.
 
+* `cu_sweep_valu` and `cu_sweep_scalar` are further launches on the same mask after each sweep launch: the
+  vector ALU, transcendentals and VGPR file (`selftest_valu.py`), and the scalar ALU, the vector / scalar boundary,
+  scalar loads and the SGPR file (`selftest_scalar.py`). Each has its own records, folded by CU like the sweep's.
+
 What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
 and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache, and of
 the matrix unit the 16x16 shapes, the sparse (smfmac) forms, bf6 operands, mixed A / B formats
@@ -32,7 +36,8 @@ runs `deep_selftest` once per candidate unit, masked to it, and says which units
 which failing CUs no such unit explains. The agent fences those units (`--selftest-fence`)
 instead of failing the device when `fenceable` allows it.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--json]` prints one report;
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--scalar all|LIST] [--json]`
+prints one report;
 with `--fence N` it also prints the units (at most N) an agent would fence, and changes nothing.
 """
 from __future__ import annotations
@@ -612,14 +617,17 @@ class DeepReport:
     cu_keys: list = field(default_factory=list, repr=False)   # sorted (xcc, cu_key) of every CU a record came from
     # {"checked": [names], "failed": {kind: [[xcc, cu_key], ...]}, "cus": fold_valu's, "reg_slots", "ms"}; None: not run
     valu: dict | None = field(default=None, repr=False)
+    # {"checked": [names], "failed": {kind: [[xcc, cu_key], ...]}, "cus": fold_scalar's, "sreg_slots", "ms"}; None: not run
+    scalar: dict | None = field(default=None, repr=False)
 
     def to_dict(self) -> dict:
         """What /metrics and --json show: every field but `cu_keys`, as before that field existed;
-        `valu` only when the vector-ALU part ran."""
+        `valu` only when the vector-ALU part ran, `scalar` only when the scalar part did."""
         d = asdict(self)
         del d["cu_keys"]
-        if d["valu"] is None:
-            del d["valu"]
+        for part in ("valu", "scalar"):
+            if d[part] is None:
+                del d[part]
         return d
 
     def describe_failure(self) -> str:
@@ -634,6 +642,10 @@ class DeepReport:
         for c in (self.valu or {}).get("cus", []):
             at = f" at slot {c['bad_slot']}, wave {c['bad_wave']} lane {c['bad_lane']}" if c["bad_slot"] >= 0 else ""
             parts.append(f"vector ALU {'+'.join(c['kinds'])} on CU (xcc {c['xcc']}, key {c['cu_key']:#x}){at}")
+        for c in (self.scalar or {}).get("cus", []):
+            at = f", at slot {c['bad_slot']}, wave {c['bad_slot_wave']}" if c["bad_slot"] >= 0 else ""
+            at += f", at word {c['bad_word']}, wave {c['bad_word_wave']}" if c["bad_word"] >= 0 else ""
+            parts.append(f"scalar unit {'+'.join(c['kinds'])} on CU (xcc {c['xcc']}, key {c['cu_key']:#x}){at}")
         if self.hbm and self.hbm.get("errors"):
             first = self.hbm.get("first") or []
             at = f", first at byte {first[0][0]} (expected {first[0][1]:#010x}, got {first[0][2]:#010x})" if first else ""
@@ -687,7 +699,7 @@ def _hbm_check(P, device: int, hbm_bytes: int, seed: int, mask: list[int], notes
 
 
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
-                  seed: int | None = None, rounds: int = 4, paths=None, valu=None) -> DeepReport:
+                  seed: int | None = None, rounds: int = 4, paths=None, valu=None, scalar=None) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
     the sweep to those CU-mask bits (the agent passes the units no tenant holds; None: the
     whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory, on a stream
@@ -695,9 +707,11 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
     (`parse_paths`: None, "all", "a,b" or a list of names) makes the sweep launches
     `cu_sweep_paths` with those matrix paths instead of `cu_sweep`: still one visit per CU.
     `valu` (`selftest_valu.parse_valu`) makes each launch of the coverage loop be followed by a
-    `cu_sweep_valu` launch of those vector-ALU groups on the same mask.
-    `ok` is false if and only if a CU failed a check, a path or a vector-ALU group, HBM errors
-    were counted, or HIP raised."""
+    `cu_sweep_valu` launch of those vector-ALU groups on the same mask. `scalar`
+    (`selftest_scalar.parse_scalar`) adds, after that, a `cu_sweep_scalar` launch of those scalar groups.
+    `ok` is false if and only if a CU failed a check, a path, a vector-ALU or a scalar group, HBM
+    errors were counted, or HIP raised."""
+    from .selftest_scalar import fold_scalar, parse_scalar
     from .selftest_valu import fold_valu, parse_valu
 
     from ..agent import cumask
@@ -713,6 +727,10 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
     if vnames and not hasattr(P, "cu_sweep_valu"):
         rep.notes.append("this probe has no cu_sweep_valu: no vector-ALU group was checked")
         vnames = []
+    snames = parse_scalar(scalar)
+    if snames and not hasattr(P, "cu_sweep_scalar"):
+        rep.notes.append("this probe has no cu_sweep_scalar: no scalar group was checked")
+        snames = []
     t0 = time.perf_counter()
     try:
         cus = int(P.device_props(device)["cus"])
@@ -720,6 +738,7 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         expected = len(set(cu_mask_bits)) if cu_mask_bits is not None else cus
         records, launches, r, last = [], 0, rounds, {}
         vrecords, vlast = [], {}
+        srecords, slast = [], {}
         while True:
             last = P.cu_sweep_paths(device, mask, r, seed, names) if names else P.cu_sweep(device, mask, r, seed)
             launches += 1
@@ -727,6 +746,9 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
             if vnames:
                 vlast = P.cu_sweep_valu(device, mask, r, seed, vnames)
                 vrecords.extend(vlast["records"])
+            if snames:
+                slast = P.cu_sweep_scalar(device, mask, r, seed, snames)
+                srecords.extend(slast["records"])
             sweep = fold_sweep([rec[:5] for rec in records], expected)
             if sweep["cus_uncovered"] == 0 or launches >= MAX_LAUNCHES:
                 break
@@ -743,12 +765,20 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
             rep.cu_keys = sorted(set(rep.cu_keys) | {(rec[0], cu_key(rec[1])) for rec in vrecords})
             if vf["cus_uncovered"]:
                 rep.notes.append(f"{vf['cus_uncovered']} CUs not reached by the vector-ALU launches")
+        if snames:
+            sf = fold_scalar(srecords, slast["groups"], expected)
+            rep.scalar = {"checked": snames, "failed": sf["failed"], "cus": sf["cus"], "sreg_slots": int(slast["sreg_slots"]),
+                          "ms": float(slast["ms"])}
+            rep.cu_keys = sorted(set(rep.cu_keys) | {(rec[0], cu_key(rec[1])) for rec in srecords})
+            if sf["cus_uncovered"]:
+                rep.notes.append(f"{sf['cus_uncovered']} CUs not reached by the scalar launches")
         if sweep["cus_uncovered"]:
             rep.notes.append(f"{sweep['cus_uncovered']} CUs not reached in {launches} launches")
         if hbm_bytes > 0:
             rep.hbm = _hbm_check(P, device, hbm_bytes, seed, mask, rep.notes)
         rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
-                  and not (rep.paths and rep.paths["failed"]) and not (rep.valu and rep.valu["failed"]))
+                  and not (rep.paths and rep.paths["failed"]) and not (rep.valu and rep.valu["failed"])
+                  and not (rep.scalar and rep.scalar["failed"]))
     except Exception as e:                     # a HIP error is a failed device
         log.exception("deep self-test of device %d raised", device)
         rep.ok, rep.error = False, f"{type(e).__name__}: {e}"
@@ -757,9 +787,9 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
 
 
 def failed_cus(report: DeepReport) -> set[tuple[int, int]]:
-    """The `(xcc, cu_key)` of every CU that failed a check or a matrix path in `report`."""
+    """The `(xcc, cu_key)` of every CU that failed a check, a matrix path, a vector-ALU or a scalar group in `report`."""
     out = {(f["xcc"], f["cu_key"]) for f in (report.sweep or {}).get("failed", [])}
-    for part in (report.paths, report.valu):
+    for part in (report.paths, report.valu, report.scalar):
         for where in ((part or {}).get("failed") or {}).values():
             out |= {(x, k) for x, k in where}
     return out
@@ -773,7 +803,7 @@ def fenceable(report: DeepReport) -> bool:
         return False
     if any("record" in f["kinds"] for f in (report.sweep or {}).get("failed", [])):
         return False
-    if "record" in ((report.paths or {}).get("failed") or {}) or "record" in ((report.valu or {}).get("failed") or {}):
+    if any("record" in ((part or {}).get("failed") or {}) for part in (report.paths, report.valu, report.scalar)):
         return False
     return bool(failed_cus(report))
 
@@ -792,10 +822,10 @@ class Localisation:
 
 
 def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_size: int, paths=None,
-                     seed: int | None = None, rounds: int = 4, valu=None) -> Localisation:
+                     seed: int | None = None, rounds: int = 4, valu=None, scalar=None) -> Localisation:
     """Which CU-mask units hold the CUs that failed in `report`. Every unit of `candidate_units`
     (unit u is mask bits [u * unit_size, (u + 1) * unit_size)) gets one `deep_selftest` masked to
-    it: the same `paths` and `valu`, no HBM check, and the same re-launch for coverage. A unit is bad when
+    it: the same `paths`, `valu` and `scalar`, no HBM check, and the same re-launch for coverage. A unit is bad when
     that run is not ok. `unexplained` lists the failed CUs of `report` that no bad unit's sweep
     ran on: a failure that did not come back, or a mask that does not reach where it lives.
     Either way a fence of the bad units would not cover it."""
@@ -803,7 +833,7 @@ def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_s
     loc = Localisation()
     for u in sorted(set(candidate_units)):
         bits = [u * unit_size + k for k in range(unit_size)]
-        r = deep_selftest(P, device, cu_mask_bits=bits, seed=seed, rounds=rounds, paths=paths, valu=valu)
+        r = deep_selftest(P, device, cu_mask_bits=bits, seed=seed, rounds=rounds, paths=paths, valu=valu, scalar=scalar)
         loc.unit_keys[u] = list(r.cu_keys)
         if r.sweep:
             loc.launches[u] = r.sweep["launches"]
@@ -817,7 +847,7 @@ def localise_failure(P, device: int, report: DeepReport, candidate_units, unit_s
     return loc
 
 
-def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None, valu=None) -> dict:
+def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None, valu=None, scalar=None) -> dict:
     """What `--fence N` prints: {"units", "cus" (unit -> its CUs), "reason" (when no unit),
     "seconds"}. Only a whole MI355X: the unit is one CU on each of its 8 XCDs."""
     from .. import types as T
@@ -829,7 +859,7 @@ def would_fence(P, device: int, report: DeepReport, max_units: int, paths=None, 
     elif not fenceable(report):
         out["reason"] = "a HIP error, HBM errors or a garbled record are not a CU's to fence"
     else:
-        loc = localise_failure(P, device, report, range(cus // T.MI355X_XCDS), T.MI355X_XCDS, paths, valu=valu)
+        loc = localise_failure(P, device, report, range(cus // T.MI355X_XCDS), T.MI355X_XCDS, paths, valu=valu, scalar=scalar)
         out["seconds"] = loc.seconds
         if loc.unexplained:
             out["reason"] = f"failing CUs {loc.unexplained} did not fail again in any unit"
@@ -856,22 +886,26 @@ def main(argv: list[str] | None = None) -> int:
                     help="matrix paths every CU also runs: 'all' or a comma-separated list of " + ", ".join(PATHS))
     ap.add_argument("--valu", default="", metavar="all|LIST",
                     help="vector-ALU groups, 'approx' and 'regs' every CU also runs: 'all' or a comma-separated list")
+    ap.add_argument("--scalar", default="", metavar="all|LIST",
+                    help="scalar-ALU groups, 'vcc', 'smem' and 'sregs' every CU also runs: 'all' or a comma-separated list")
     ap.add_argument("--fence", type=int, default=0, metavar="N",
                     help="after a failed sweep, print the CU-mask units (at most N) and CUs an agent started with "
                          "--selftest-fence N would fence; changes nothing on the device or the node")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args(argv)
     try:
+        from .selftest_scalar import parse_scalar
         from .selftest_valu import parse_valu
 
         names = parse_paths(a.paths)
         vnames = parse_valu(a.valu)
+        snames = parse_scalar(a.scalar)
     except ValueError as e:
         ap.error(str(e))
     P = probe(required=True)
     nbytes = free_hbm_bytes(P, a.device, a.hbm_mib)
-    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names, valu=vnames)
-    plan = would_fence(P, a.device, rep, a.fence, names, valu=vnames) if a.fence > 0 and not rep.ok else None
+    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, paths=names, valu=vnames, scalar=snames)
+    plan = would_fence(P, a.device, rep, a.fence, names, valu=vnames, scalar=snames) if a.fence > 0 and not rep.ok else None
     if a.json:
         print(json.dumps(dict(rep.to_dict(), fence=plan) if a.fence > 0 else rep.to_dict()))
     else:
@@ -890,6 +924,8 @@ def main(argv: list[str] | None = None) -> int:
             print_named("matrix paths", rep.paths)
         if rep.valu:
             print_named("vector ALU", rep.valu, f" ({rep.valu['reg_slots']} registers a lane, {rep.valu['ms']:.3f} ms)")
+        if rep.scalar:
+            print_named("scalar unit", rep.scalar, f" ({rep.scalar['sreg_slots']} registers a wave, {rep.scalar['ms']:.3f} ms)")
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
                   f"verify {h['verify_gbs']:.0f} GB/s, {h.get('verify_launches', 1)} launch(es) a pass")
