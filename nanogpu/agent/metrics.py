@@ -45,6 +45,8 @@ from __future__ import annotations
 
 from pathlib import Path
 
+from ..probe.selftest import PARTS
+
 
 def _esc(v) -> str:
     return str(v).replace("\\", "\\\\").replace('"', '\\"').replace("\n", "\\n")
@@ -172,18 +174,14 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
                rows(lambda r: r.get("seconds", 0)))
         family("nanogpu_selftest_runs_total", "counter", "deep self-tests run, by result",
                [(_labels(device=i, result=res), n) for (i, res), n in sorted(selftest.get("runs", {}).items())])
-        with_paths = [(i, r["paths"]) for i, r in reps if r.get("paths")]
-        family("nanogpu_selftest_paths_checked", "gauge", "matrix paths the last deep self-test ran on every CU",
-               [(_labels(device=i), len(p["checked"])) for i, p in with_paths])
-        family("nanogpu_selftest_path_cus_failed", "gauge", "CUs that failed the matrix path in the last deep self-test",
-               [(_labels(device=i, path=name), len(p["failed"].get(name, [])))
-                for i, p in with_paths for name in p["checked"]])
-        family("nanogpu_selftest_valu_checked", "gauge",
-               "vector-ALU groups (with approx and regs) the last deep self-test ran on every CU",
-               [(_labels(device=i), len(r["valu"]["checked"])) for i, r in reps if r.get("valu")])
-        family("nanogpu_selftest_scalar_checked", "gauge",
-               "scalar groups (with smem and sregs) the last deep self-test ran on every CU",
-               [(_labels(device=i), len(r["scalar"]["checked"])) for i, r in reps if r.get("scalar")])
+        for part in PARTS:
+            ran = [(i, r[part.key]) for i, r in reps if r.get(part.key)]
+            family(f"nanogpu_selftest_{part.key}_checked", "gauge", part.metric_help,
+                   [(_labels(device=i), len(p["checked"])) for i, p in ran])
+            if part.failed_metric:
+                name, label, help_ = part.failed_metric
+                family(name, "gauge", help_, [(_labels(device=i, **{label: n}), len(p["failed"].get(n, [])))
+                                              for i, p in ran for n in p["checked"]])
     if fence is not None:
         def per_device(key):
             return [(_labels(device=i), v) for i, v in sorted(fence.get(key, {}).items())]

@@ -154,20 +154,13 @@ class NodeAgent:
         self.selftest_deep = selftest_deep       # probe.selftest.deep_selftest instead of gpu_selftest
         self.selftest_hbm_mib = selftest_hbm_mib  # cap of the HBM pattern check (0: free HBM less 2 GiB)
         self.selftest_period_s = selftest_period_s
-        from ..probe.selftest import parse_paths
-        from ..probe.selftest_scalar import parse_scalar
-        from ..probe.selftest_valu import parse_valu
+        from ..probe.selftest import Selection
 
-        def part_of_deep(parse, spec) -> list[str]:   # "all", "a,b" or names; any of them makes the sweep deep
-            names = parse(spec)
-            if names:
-                self.selftest_deep = True
-            return names
-
-        self.selftest_paths = part_of_deep(parse_paths, selftest_paths)   # matrix paths every deep sweep also runs
+        # what every deep sweep also runs of each optional part ("all", "a,b" or names); any of them makes the sweep deep
+        self.selftest_parts = Selection.parse(paths=selftest_paths, valu=selftest_valu, scalar=selftest_scalar)
+        if any(vars(self.selftest_parts).values()):
+            self.selftest_deep = True
         self._no_paths_logged = False
-        self.selftest_valu = part_of_deep(parse_valu, selftest_valu)      # vector-ALU groups, 'approx' and 'regs'
-        self.selftest_scalar = part_of_deep(parse_scalar, selftest_scalar)   # scalar groups, 'smem' and 'sregs'
         # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
         # CU-mask units that hold them (at most this many a device) instead of its health (`_deep_fenced`)
         self.selftest_fence = max(0, int(selftest_fence))
@@ -413,7 +406,7 @@ class NodeAgent:
                     nbytes = free_hbm_bytes(P, i, self.selftest_hbm_mib)
                 except Exception:              # the sweep below reports a device that cannot answer
                     log.exception("agent %s: memory info of device %d failed", self.node, i)
-            if self.selftest_paths and not hasattr(P, "cu_sweep_paths") and not self._no_paths_logged:
+            if self.selftest_parts.paths and not hasattr(P, "cu_sweep_paths") and not self._no_paths_logged:
                 self._no_paths_logged = True
                 log.warning("agent %s: this probe has no cu_sweep_paths: the deep self-test runs without the "
                             "matrix paths", self.node)
@@ -421,8 +414,7 @@ class NodeAgent:
             if self.selftest_fence and self.plugin is not None and self._is_spx(i):
                 r, fenced_now = self._deep_fenced(P, i, bits, nbytes)
             else:
-                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=self.selftest_paths, valu=self.selftest_valu,
-                                  scalar=self.selftest_scalar)
+                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, **vars(self.selftest_parts))
             reports[i] = r
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
@@ -448,16 +440,15 @@ class NodeAgent:
         from ..probe.selftest import deep_selftest, failed_cus, fenceable, localise_failure
 
         dc = self.plugin.cus[i]
-        paths = self.selftest_paths
-        valu, scalar = self.selftest_valu, self.selftest_scalar
-        sweep = deep_selftest(P, i, cu_mask_bits=bits, paths=paths, valu=valu, scalar=scalar)
+        select = vars(self.selftest_parts)
+        sweep = deep_selftest(P, i, cu_mask_bits=bits, **select)
         if sweep.ok:
-            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, paths=paths, valu=valu, scalar=scalar) if nbytes else sweep), False
+            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, **select) if nbytes else sweep), False
         if not fenceable(sweep):
             return sweep, False
         all_bits = bits if bits is not None else list(range(dc.cus))
         units = sorted({b // dc.unit for b in all_bits} - dc.fenced)
-        loc = localise_failure(P, i, sweep, units, dc.unit, paths, valu=valu, scalar=scalar)
+        loc = localise_failure(P, i, sweep, units, dc.unit, **select)
         self.localise_seconds[i] = loc.seconds
         bad = set(loc.bad_units)
         why = (f"CUs {loc.unexplained} failed and no unit swept alone explains them" if loc.unexplained
@@ -469,7 +460,7 @@ class NodeAgent:
             log.warning("agent %s: device %d is not fenced: %s", self.node, i, why)
             return sweep, False
         verify = deep_selftest(P, i, cu_mask_bits=[b for b in all_bits if b // dc.unit not in bad],
-                               hbm_bytes=nbytes, paths=paths, valu=valu, scalar=scalar)
+                               hbm_bytes=nbytes, **select)
         stray = sorted(set(verify.cu_keys) & failed_cus(sweep))
         if verify.ok and stray:
             verify.ok = False
@@ -642,37 +633,21 @@ def build_parser():
     ap.add_argument("--selftest-deep", action=_Deep, nargs=0, default=False,
                     help="the start-up self-test checks every CU (MFMA pipes, LDS) and the free HBM with an "
                          "address-derived pattern instead of one tile and 16 MiB (implies --selftest)")
-    from ..probe.selftest import parse_paths
-    from ..probe.selftest_scalar import parse_scalar
-    from ..probe.selftest_valu import parse_valu
+    from ..probe.selftest import PARTS
 
-    def names_action(parse, noun: str):        # --selftest-paths, --selftest-valu and --selftest-scalar imply --selftest-deep
-        class _Names(argparse.Action):
-            def __call__(self, parser, ns, values, option_string=None):
-                try:
-                    setattr(ns, self.dest, parse(values))
-                except ValueError as e:
-                    parser.error(f"{option_string}: {e}")
-                if not getattr(ns, self.dest):
-                    parser.error(f"{option_string}: name at least one {noun}, or 'all'")
-                ns.selftest = ns.selftest_deep = True
+    class _Names(argparse.Action):             # the flag of a part (its `const`) of the deep self-test implies --selftest-deep
+        def __call__(self, parser, ns, values, option_string=None):
+            try:
+                setattr(ns, self.dest, self.const.parse(values))
+            except ValueError as e:
+                parser.error(f"{option_string}: {e}")
+            if not getattr(ns, self.dest):
+                parser.error(f"{option_string}: name at least one {self.const.flag_noun}, or 'all'")
+            ns.selftest = ns.selftest_deep = True
 
-        return _Names
-
-    ap.add_argument("--selftest-paths", action=names_action(parse_paths, "path"), default=[], metavar="all|LIST",
-                    help="the deep self-test also runs an exact MFMA chain of these matrix paths on every CU: "
-                         "'all' or a comma-separated list of f16, fp8, bf8, i8, mxfp8, mxfp6, mxfp4, f32, f64 "
-                         "(implies --selftest-deep; start-up and periodic runs alike)")
-    ap.add_argument("--selftest-valu", action=names_action(parse_valu, "group"), default=[], metavar="all|LIST",
-                    help="the deep self-test also runs, on all four SIMDs of every CU, exact chains of vector-ALU "
-                         "instructions, the transcendentals and a pattern test of the vector register file: 'all' or a "
-                         "comma-separated list of fma32, fma64, pkfma16, pkfma32, addmul32, int32, int64, bits, dot, "
-                         "cvt, xlane, approx, regs (implies --selftest-deep; start-up and periodic runs alike)")
-    ap.add_argument("--selftest-scalar", action=names_action(parse_scalar, "group"), default=[], metavar="all|LIST",
-                    help="the deep self-test also runs, on all four waves of every CU, exact chains of scalar-ALU "
-                         "instructions, the vector / scalar boundary, scalar loads of every width and a pattern test of the "
-                         "wave's scalar registers: 'all' or a comma-separated list of add, mul, shift, logic, bits, cmp, "
-                         "vcc, smem, sregs (implies --selftest-deep; start-up and periodic runs alike)")
+    for part in PARTS:
+        ap.add_argument(f"--selftest-{part.key}", action=_Names, const=part, default=[], metavar="all|LIST",
+                        help=part.agent_help)
 
     class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
         def __call__(self, parser, ns, values, option_string=None):
@@ -720,15 +695,16 @@ def main(argv: list[str] | None = None) -> int:
         import signal
 
         from ..k8s.client import KubeClient, KubeConfig
+        from ..probe.selftest import PARTS
 
         api = KubeClient(KubeConfig.auto(a.kubeconfig, a.kube_api))
         agent = NodeAgent(api, a.node_name, topo, host, device_plugin=a.advertise == "device-plugin",
                           plugin_dir=a.plugin_dir, sysfs_root=a.sysfs_root,
                           pod_resources_socket=a.pod_resources_socket, reconcile_period_s=a.reconcile_period,
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
-                          selftest_period_s=a.selftest_period, selftest_paths=a.selftest_paths, selftest_valu=a.selftest_valu,
-                          selftest_scalar=a.selftest_scalar,
-                          selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset)
+                          selftest_period_s=a.selftest_period,
+                          selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset,
+                          **{name: getattr(a, name) for name in (f"selftest_{part.key}" for part in PARTS)})
         await agent.start()
         if a.selftest:
             failed = await agent.selftest()

@@ -16,7 +16,8 @@ width 0, and find-first / find-leading-bit of an operand without the bit sought.
 """
 from __future__ import annotations
 
-from .selftest import M32, _by_cu, _named_failures, _parse_names, _simds_seen_min, mix32, tile_checksum
+from .selftest_common import (HI_MUL, M32, M64, Part, by_cu, mix32, named_failures, parse_names, rotl32, simds_seen_min,
+                              tile_checksum)
 
 GROUPS = ("add", "mul", "shift", "logic", "bits", "cmp", "vcc", "smem", "sregs")   # bit order of the records
 NUM_EXACT = 7
@@ -29,8 +30,6 @@ SREG_FIRST = 12
 SMEM_WORDS = 4096
 SMEM_SALT = 0x51ED270B
 RECORD_WORDS = 8
-M64 = (1 << 64) - 1
-HI_MUL = 0x9E3779B1
 ZERO_STEP, EQUAL_STEP = 5, 2
 # fail bits, by wave: exact groups, scalar loads, scalar registers
 FAIL_EXACT, FAIL_SMEM, FAIL_SREGS = 0xF, 0xF0, 0xF00
@@ -38,17 +37,12 @@ BAD_SREGS, BAD_SMEM = 0, 1
 
 
 def parse_scalar(spec) -> list[str]:
-    """`_parse_names` over `GROUPS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
-    return _parse_names(spec, GROUPS, "scalar group")
+    """`parse_names` over `GROUPS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
+    return parse_names(spec, GROUPS, "scalar group")
 
 
 def operand(group: str, s: int, wave: int, k: int) -> int:
     return mix32(0x5CA1A2B3 ^ (GROUPS.index(group) << 24) ^ (s << 16) ^ (wave << 8) ^ k)
-
-
-def rotl32(x: int, r: int) -> int:
-    r &= 31
-    return ((x << r) | (x >> (32 - r))) & M32 if r else x & M32
 
 
 def fold(h: int, d: int, c: int) -> int:
@@ -552,9 +546,9 @@ def fold_scalar(records, groups, expected_cus) -> dict:
     (-1: none). `uncovered` / `cus_uncovered` as in `fold_sweep`: not a failure."""
     groups = list(groups)
     n_exact = len([g for g in groups if g not in ("smem", "sregs")])
-    by_cu = _by_cu([tuple(r) for r in records])
+    cus = by_cu([tuple(r) for r in records])
     failures = []
-    for k, visits in sorted(by_cu.items()):
+    for k, visits in sorted(cus.items()):
         found, waves = set(), 0
         first = {BAD_SREGS: (-1, -1), BAD_SMEM: (-1, -1)}
         for fail, _simds, gbits, index, wave, which in visits:
@@ -575,7 +569,24 @@ def fold_scalar(records, groups, expected_cus) -> dict:
             failures.append((k, kinds, {"kinds": kinds, "waves": waves, "bad_slot": first[BAD_SREGS][0],
                                         "bad_slot_wave": first[BAD_SREGS][1], "bad_word": first[BAD_SMEM][0],
                                         "bad_word_wave": first[BAD_SMEM][1]}))
-    return dict(_named_failures(by_cu, expected_cus, failures), simds_seen_min=_simds_seen_min(by_cu, 1))
+    return dict(named_failures(cus, expected_cus, failures), simds_seen_min=simds_seen_min(cus, 1))
+
+
+PART = Part(
+    key="scalar", names=GROUPS, noun="scalar group", flag_noun="group", binding="cu_sweep_scalar", names_key="groups",
+    fold=fold_scalar, kept=("cus", "sreg_slots", "ms"), label="scalar unit", detail=" ({sreg_slots} registers a wave, {ms:.3f} ms)",
+    clauses=lambda d: [f"scalar unit {'+'.join(c['kinds'])} on CU (xcc {c['xcc']}, key {c['cu_key']:#x})"
+                       + (f", at slot {c['bad_slot']}, wave {c['bad_slot_wave']}" if c["bad_slot"] >= 0 else "")
+                       + (f", at word {c['bad_word']}, wave {c['bad_word_wave']}" if c["bad_word"] >= 0 else "")
+                       for c in d.get("cus", [])],
+    note_missing="this probe has no cu_sweep_scalar: no scalar group was checked",
+    note_unreached="{n} CUs not reached by the scalar launches",
+    help="scalar-ALU groups, 'vcc', 'smem' and 'sregs' every CU also runs: 'all' or a comma-separated list",
+    agent_help="the deep self-test also runs, on all four waves of every CU, exact chains of scalar-ALU "
+               "instructions, the vector / scalar boundary, scalar loads of every width and a pattern test of the "
+               "wave's scalar registers: 'all' or a comma-separated list of add, mul, shift, logic, bits, cmp, "
+               "vcc, smem, sregs (implies --selftest-deep; start-up and periodic runs alike)",
+    metric_help="scalar groups (with smem and sregs) the last deep self-test ran on every CU")
 
 
 def twin_summary() -> dict:

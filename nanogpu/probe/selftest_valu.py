@@ -13,7 +13,8 @@ import math
 import struct
 from fractions import Fraction
 
-from .selftest import M32, _by_cu, _named_failures, _parse_names, _simds_seen_min, mix32, tile_checksum
+from .selftest_common import (M32, M64, Part, by_cu, mix32, named_failures, parse_names, rotl32, simds_seen_min,
+                              tile_checksum)
 
 GROUPS = ("fma32", "fma64", "pkfma16", "pkfma32", "addmul32", "int32", "int64", "bits", "dot", "cvt", "xlane",
           "approx", "regs")                      # bit order of the records
@@ -26,7 +27,6 @@ APPROX_OPS = ("exp2", "log2", "rcp", "rsq", "sqrt")
 APPROX_ULPS = 8
 REG_SLOTS = 448
 RECORD_WORDS = 8
-M64 = (1 << 64) - 1
 EXP_A, EXP_B, EXP_X0 = -3, 0, 0
 # fail bits, by wave: exact groups, register file, approx bound, approx hash unlike wave 0's
 FAIL_EXACT, FAIL_REGS, FAIL_BOUND, FAIL_HASH = 0xF, 0xF0, 0xF00, 0xF000
@@ -35,8 +35,8 @@ F64, F32, F16, BF16, E4M3, E5M2 = (53, 11, 1023), (24, 8, 127), (11, 5, 15), (8,
 
 
 def parse_valu(spec) -> list[str]:
-    """`_parse_names` over `GROUPS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
-    return _parse_names(spec, GROUPS, "vector-ALU group")
+    """`parse_names` over `GROUPS`: None / "" -> [], "all", "a,b" or a list of names; ValueError on an unknown one."""
+    return parse_names(spec, GROUPS, "vector-ALU group")
 
 
 def operand(group: str, s: int, lane: int, k: int) -> int:
@@ -57,11 +57,6 @@ def f16_win(u: int, e: int) -> int:
 
 def f16x2_win(u: int, e: int) -> int:
     return f16_win(u & 0xFFFF, e) | (f16_win(u >> 16, e) << 16)
-
-
-def rotl32(x: int, r: int) -> int:
-    r &= 31
-    return ((x << r) | (x >> (32 - r))) & M32 if r else x & M32
 
 
 class Conds:
@@ -485,9 +480,9 @@ def fold_valu(records, groups, expected_cus) -> dict:
     for r in records:
         counts[r[7]] = counts.get(r[7], 0) + 1
     majority = next((h for h, n in counts.items() if 2 * n > len(records)), None)
-    by_cu = _by_cu(records)
+    cus = by_cu(records)
     failures = []
-    for k, visits in sorted(by_cu.items()):
+    for k, visits in sorted(cus.items()):
         found, waves, slot, thread = set(), 0, -1, -1
         for fail, _simds, gbits, s, t, ahash in visits:
             if fail >> 16 or gbits >> n_exact or bool(fail & FAIL_EXACT) != bool(gbits) or bool(fail & FAIL_REGS) != (s >= 0):
@@ -507,8 +502,24 @@ def fold_valu(records, groups, expected_cus) -> dict:
             failures.append((k, kinds, {"kinds": kinds, "waves": waves, "bad_slot": slot,
                                         "bad_wave": thread >> 6 if thread >= 0 else -1,
                                         "bad_lane": thread & 63 if thread >= 0 else -1}))
-    return dict(_named_failures(by_cu, expected_cus, failures), approx_hash=majority,
-                simds_seen_min=_simds_seen_min(by_cu, 1))
+    return dict(named_failures(cus, expected_cus, failures), approx_hash=majority,
+                simds_seen_min=simds_seen_min(cus, 1))
+
+
+PART = Part(
+    key="valu", names=GROUPS, noun="vector-ALU group", flag_noun="group", binding="cu_sweep_valu", names_key="groups",
+    fold=fold_valu, kept=("cus", "reg_slots", "ms"), label="vector ALU", detail=" ({reg_slots} registers a lane, {ms:.3f} ms)",
+    clauses=lambda d: [f"vector ALU {'+'.join(c['kinds'])} on CU (xcc {c['xcc']}, key {c['cu_key']:#x})"
+                       + (f" at slot {c['bad_slot']}, wave {c['bad_wave']} lane {c['bad_lane']}" if c["bad_slot"] >= 0 else "")
+                       for c in d.get("cus", [])],
+    note_missing="this probe has no cu_sweep_valu: no vector-ALU group was checked",
+    note_unreached="{n} CUs not reached by the vector-ALU launches",
+    help="vector-ALU groups, 'approx' and 'regs' every CU also runs: 'all' or a comma-separated list",
+    agent_help="the deep self-test also runs, on all four SIMDs of every CU, exact chains of vector-ALU "
+               "instructions, the transcendentals and a pattern test of the vector register file: 'all' or a "
+               "comma-separated list of fma32, fma64, pkfma16, pkfma32, addmul32, int32, int64, bits, dot, "
+               "cvt, xlane, approx, regs (implies --selftest-deep; start-up and periodic runs alike)",
+    metric_help="vector-ALU groups (with approx and regs) the last deep self-test ran on every CU")
 
 
 def twin_summary() -> dict:

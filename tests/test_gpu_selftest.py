@@ -59,7 +59,8 @@ def test_sweep_reaches_every_cu_and_whole_lds(P, clean):
 
 def test_masked_sweep_sees_the_cus_the_census_sees(P):
     from nanogpu.agent import cumask
-    from nanogpu.probe.selftest import cu_key, fold_sweep
+    from nanogpu.probe.selftest import fold_sweep
+    from nanogpu.probe.selftest_common import cu_key
 
     bits = cumask.DeviceCUs(256, 8).grant("t", 25)
     words = cumask.mask_words(bits)
@@ -74,7 +75,7 @@ def test_masked_sweep_sees_the_cus_the_census_sees(P):
 
 
 def _a_cu_on_xcd3(rep_records):
-    from nanogpu.probe.selftest import cu_key
+    from nanogpu.probe.selftest_common import cu_key
 
     return sorted({cu_key(h) for x, h, *_ in rep_records if x == 3})[5]
 
@@ -110,7 +111,8 @@ def test_injected_lds_fault_reports_the_offset(P, clean, where):
 def test_two_injected_cus_fold_to_two_cus_with_their_own_offsets(P, clean):
     """Two runs, each with one CU injected at its own LDS dword, folded together: fold_sweep
     keeps both CUs and gives each the offset that was put into it."""
-    from nanogpu.probe.selftest import cu_key, fold_sweep
+    from nanogpu.probe.selftest import fold_sweep
+    from nanogpu.probe.selftest_common import cu_key
 
     n = clean[0]["lds_bytes"] // 4
     keys5 = sorted({cu_key(h) for x, h, *_ in clean[0]["records"] if x == 5})

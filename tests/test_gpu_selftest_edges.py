@@ -1,5 +1,5 @@
 """Every operand code and every E8M0 scale, once, on a real MI355X (`pytest -m gpu`):
-`matrix_tile` on the edge tiles of nanogpu.probe.selftest.edge_tiles, bit-equal with the twin's
+`matrix_tile` on the edge tiles of nanogpu.probe.selftest_paths.edge_tiles, bit-equal with the twin's
 exact product. Every accumulator of such a tile has one term at most, so the result is exact in
 any order and the tiles may hold what the sweep's generators exclude: zero, subnormals, the
 largest normals, every code of the narrow formats, and scales 0..254 in every byte of the scale
@@ -31,9 +31,9 @@ def P():
 
 
 def code_class(path, code):
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
-    ebits, mbits, _bias = S.PATH_FORMAT[path]
+    ebits, mbits, _bias = SP.PATH_FORMAT[path]
     if not ebits:
         return "int"
     mag = code & ((1 << (ebits + mbits)) - 1)
@@ -42,11 +42,11 @@ def code_class(path, code):
 
 def describe(path, a, b, sa, sb, at):
     """(class of A's code, class of B's code) and the operands of accumulator `at`'s one term."""
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
-    dim = S.path_dim(path)
+    dim = SP.path_dim(path)
     r, c = divmod(at, dim)
-    ks = [k for k in range(S.PATH_K[path]) if a[r][k] and b[k][c]]
+    ks = [k for k in range(SP.PATH_K[path]) if a[r][k] and b[k][c]]
     if not ks:
         return ("no term", "no term"), None
     k = ks[0]
@@ -60,7 +60,7 @@ def describe(path, a, b, sa, sb, at):
 def test_matrix_tile_is_exact_on_every_code_and_every_scale(P, path):
     """The expected value is the OCP value of the one term; an accumulator without a term, or
     whose term is +-0, holds +0."""
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
     per = 2 if path == "f64" else 1
     t0 = time.perf_counter()
@@ -69,10 +69,10 @@ def test_matrix_tile_is_exact_on_every_code_and_every_scale(P, path):
     examples = []
     codes = [set(), set()]
     scales = [set(), set()]
-    for a, b, sa, sb, opsel in S.edge_tiles(path):
-        want = S.product_words(path, a, b, sa, sb)
+    for a, b, sa, sb, opsel in SP.edge_tiles(path):
+        want = SP.product_words(path, a, b, sa, sb)
         args = [] if sa is None else [[v for row in sa for v in row], [v for row in sb for v in row], opsel]
-        got = S.tile_words(path, P.matrix_tile(path, [c for row in a for c in row], [c for row in b for c in row], *args))
+        got = SP.tile_words(path, P.matrix_tile(path, [c for row in a for c in row], [c for row in b for c in row], *args))
         assert len(got) == len(want)
         tiles += 1
         accumulators += len(want) // per

@@ -44,7 +44,7 @@ def P():
 @pytest.fixture(scope="module")
 def cu_on_xcd3(P):
     """The CU the injections go to, picked as tests/test_gpu_selftest.py picks it."""
-    from nanogpu.probe.selftest import cu_key
+    from nanogpu.probe.selftest_common import cu_key
 
     r = P.cu_sweep(0, [], 8, SEED)
     return sorted({cu_key(h) for x, h, *_ in r["records"] if x == 3})[5]
@@ -66,7 +66,7 @@ class Injecting:
         return 1
 
     def _keep(self, name, mask, rounds, r):
-        from nanogpu.probe.selftest import cu_key
+        from nanogpu.probe.selftest_common import cu_key
 
         self.calls.append((name, list(mask), rounds, {(rec[0], cu_key(rec[1])) for rec in r["records"]}))
         return r
@@ -86,7 +86,7 @@ def _localise(P, inject, paths):
     rep = deep_selftest(proxy, 0, seed=SEED, paths=paths)
     assert not rep.ok and fenceable(rep), rep.to_dict()
     assert failed_cus(rep) == {(inject[0], inject[1])}
-    loc = localise_failure(proxy, 0, rep, range(UNITS), UNIT, paths, seed=SEED)
+    loc = localise_failure(proxy, 0, rep, range(UNITS), UNIT, paths=paths, seed=SEED)
     print("localisation:", inject[2], paths, round(loc.seconds, 4), "s, launches", loc.launches, "uncovered", loc.uncovered)
     return loc
 
@@ -181,7 +181,7 @@ _CHILD = r'''
 import json, os, sys
 sys.path.insert(0, os.environ["REPO"])
 from nanogpu.native import probe
-from nanogpu.probe.selftest import cu_key
+from nanogpu.probe.selftest_common import cu_key
 P = probe(required=True)
 want, seed = int(os.environ["WANT_CUS"]), int(os.environ["SEED"])
 keys, rounds = set(), 8
@@ -196,7 +196,7 @@ print(json.dumps(sorted(keys)))
 
 def _masked_keys(P, bits, want):
     from nanogpu.agent import cumask
-    from nanogpu.probe.selftest import cu_key
+    from nanogpu.probe.selftest_common import cu_key
 
     keys, rounds = set(), 8
     for _ in range(3):

@@ -28,7 +28,7 @@ def P():
 
 
 def _paths():
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     return list(PATHS)
 
@@ -80,7 +80,8 @@ def test_path_part_kernel_compares_the_path_tiles(P, flip):
 
 def test_the_dynamic_size_reaches_the_lds_test(P, clean_plain):
     """The last dword of a 9,216-dword array, on the CU the clean run visited most often."""
-    from nanogpu.probe.selftest import cu_key, fold_sweep
+    from nanogpu.probe.selftest import fold_sweep
+    from nanogpu.probe.selftest_common import cu_key
 
     n = STAGED // 4
     (xcc, key), _visits = Counter((x[0], cu_key(x[1])) for x in clean_plain["records"]).most_common(1)[0]

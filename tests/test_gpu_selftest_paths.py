@@ -35,7 +35,8 @@ def P():
 def _sweep_all(P, rounds=4, inject=None):
     """One unmasked path sweep with deep_selftest's own policy for coverage (a shortfall is not
     a failure: doubled rounds, three launches at most)."""
-    from nanogpu.probe.selftest import PATHS, fold_paths, fold_sweep
+    from nanogpu.probe.selftest import fold_sweep
+    from nanogpu.probe.selftest_paths import PATHS, fold_paths
 
     r = P.cu_sweep_paths(0, [], rounds, SEED, list(PATHS), inject)
     records = list(r["records"])
@@ -58,17 +59,17 @@ def _random_codes(path, rng, step):
     formats draw sign, mantissa and the window's exponents freely. f16 / f32 / f64 hold one
     full-mantissa value per accumulator, as the sweep's generators do (wide_code with a random
     hash): step 0 puts it in A, step 1 in B."""
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
-    dim, K, cb = S.path_dim(path), S.PATH_K[path], S.PATH_CODE_BITS[path]
-    ebits, mbits, bias = S.PATH_FORMAT[path]
+    dim, K, cb = SP.path_dim(path), SP.PATH_K[path], SP.PATH_CODE_BITS[path]
+    ebits, mbits, bias = SP.PATH_FORMAT[path]
 
     def code(op, idx, k):
         if path == "i8":
             return rng.getrandbits(8)
         if path in ("f16", "f32", "f64"):
-            return S.wide_code(cb, mbits, bias, op, step, idx, k, rng.getrandbits(cb))
-        e = rng.choice(S.PATH_EXP_WINDOW[path])
+            return SP.wide_code(cb, mbits, bias, op, step, idx, k, rng.getrandbits(cb))
+        e = rng.choice(SP.PATH_EXP_WINDOW[path])
         return (rng.getrandbits(1) << (ebits + mbits)) | (e << mbits) | rng.getrandbits(mbits)
 
     a = [[code(0, r, k) for k in range(K)] for r in range(dim)]
@@ -79,10 +80,10 @@ def _random_codes(path, rng, step):
 def _assert_exact(path, abs_units):
     """The instruction's own exactness condition: every term is a multiple of the unit (the lowest
     set bit of the sums of |term|), and no accumulator's sum of |term| reaches the limit."""
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
-    tz = min(S._trailing_zeros(v) for row in abs_units for v in row if v)
-    assert max(v >> tz for row in abs_units for v in row) < 1 << S.PATH_LIMIT_BITS.get(path, 24)
+    tz = min(SP._trailing_zeros(v) for row in abs_units for v in row if v)
+    assert max(v >> tz for row in abs_units for v in row) < 1 << SP.PATH_LIMIT_BITS.get(path, 24)
 
 
 @pytest.mark.parametrize("path", ["f16", "fp8", "bf8", "i8", "mxfp8", "mxfp6", "mxfp4", "f32", "f64"])
@@ -90,24 +91,24 @@ def test_matrix_tile_is_the_exact_product(P, path):
     """Every lane, every register and both k halves of one tile, on asymmetric random codes and
     scales: bit-equal with the twin's integer product. A wrong operand or C lane map, a wrong
     code packing or a scale taken from another block or byte cannot pass."""
-    from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_paths as SP
 
-    rng = random.Random(SEED ^ S.PATHS.index(path))
-    dim = S.path_dim(path)
+    rng = random.Random(SEED ^ SP.PATHS.index(path))
+    dim = SP.path_dim(path)
     for step, opsel in ((0, (0, 0)), (1, (2, 1))):
         a, b = _random_codes(path, rng, step)
         sa = sb = None
         args = []
-        if path in S.SCALED_PATHS:
-            sa = [[rng.choice(S.SCALE_WINDOW) for _ in range(2)] for _ in range(dim)]
-            sb = [[rng.choice(S.SCALE_WINDOW) for _ in range(dim)] for _ in range(2)]
+        if path in SP.SCALED_PATHS:
+            sa = [[rng.choice(SP.SCALE_WINDOW) for _ in range(2)] for _ in range(dim)]
+            sb = [[rng.choice(SP.SCALE_WINDOW) for _ in range(dim)] for _ in range(2)]
             args = [[v for row in sa for v in row], [v for row in sb for v in row], opsel]
         assert a != [[b[k][i] for k in range(len(b))] for i in range(dim)]          # asymmetric
-        units, abs_units, unit_exp = S.exact_product(path, a, b, sa, sb)
+        units, abs_units, unit_exp = SP.exact_product(path, a, b, sa, sb)
         _assert_exact(path, abs_units)
-        want = S.tile_words(path, S.tile_values(path, [u for row in units for u in row], unit_exp))
+        want = SP.tile_words(path, SP.tile_values(path, [u for row in units for u in row], unit_exp))
         got = P.matrix_tile(path, [c for row in a for c in row], [c for row in b for c in row], *args)
-        got_words = S.tile_words(path, got)
+        got_words = SP.tile_words(path, got)
         wrong = [i for i in range(len(want)) if want[i] != got_words[i]]
         print(path, "step", step, "opsel", opsel, "wrong words", len(wrong), "of", len(want), wrong[:8])
         assert got_words == want, (path, step, len(wrong), wrong[:8])
@@ -115,7 +116,7 @@ def test_matrix_tile_is_the_exact_product(P, path):
 
 # ----------------------------------------------------------------------------- the sweep
 def test_path_sweep_reaches_every_cu_and_every_path_is_clean(P, clean):
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     r, rep, paths = clean
     print("path sweep:", rep["cus_seen"], rep["per_xcd"], r["lds_bytes"], r["ms"], paths["failed"])
@@ -127,7 +128,7 @@ def test_path_sweep_reaches_every_cu_and_every_path_is_clean(P, clean):
 
 
 def _a_cu_on_xcd3(records):
-    from nanogpu.probe.selftest import cu_key
+    from nanogpu.probe.selftest_common import cu_key
 
     return sorted({cu_key(x[1]) for x in records if x[0] == 3})[5]
 
@@ -143,7 +144,9 @@ def test_injected_path_fault_fails_exactly_that_cu_and_path(P, clean, path):
 
 def test_masked_path_sweep_sees_the_cus_the_census_sees(P):
     from nanogpu.agent import cumask
-    from nanogpu.probe.selftest import PATHS, cu_key, fold_paths, fold_sweep
+    from nanogpu.probe.selftest import fold_sweep
+    from nanogpu.probe.selftest_common import cu_key
+    from nanogpu.probe.selftest_paths import PATHS, fold_paths
 
     words = cumask.mask_words(cumask.DeviceCUs(256, 8).grant("t", 25))
     census = {(x, cu_key(h)) for x, h in P.cu_census(0, words, 2048, 64)}
@@ -162,7 +165,8 @@ def test_deep_selftest_with_paths_and_agent_on_the_real_device(P):
     from nanogpu.agent.metrics import render
     from nanogpu.agent.node import NodeAgent
     from nanogpu.native import core
-    from nanogpu.probe.selftest import PATHS, deep_selftest
+    from nanogpu.probe.selftest import deep_selftest
+    from nanogpu.probe.selftest_paths import PATHS
     from nanogpu.topology.model import from_host_json
 
     rep = deep_selftest(P, 0, paths="all", hbm_bytes=256 << 20)
@@ -190,7 +194,7 @@ def test_a_path_visit_costs_no_more_than_a_plain_one(P):
     unmasked and at the 25 % mask: the path sweep's median is at most the plain one's plus
     10 %, the run-to-run spread test_pattern_verify_keeps_up_with_the_copy allows on this box."""
     from nanogpu.agent import cumask
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     words = cumask.mask_words(cumask.DeviceCUs(256, 8).grant("t", 25))
     out = {}

@@ -82,10 +82,11 @@ def test_injection_fails_exactly_that_cu_and_kind(P, clean, kind, arg):
     """An exact group and the registers are corrupted on wave 0. A table word is read by one wave only (wave w
     reads quarter w), so word 4095 fails on wave 3, the wave that compares it, and word 0 on wave 0."""
     from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_common as C
     from nanogpu.probe.selftest_scalar import GROUPS
 
     rec = clean[0]["records"][len(clean[0]["records"]) // 3]
-    cu = (rec[0], S.cu_key(rec[1]))
+    cu = (rec[0], C.cu_key(rec[1]))
     r, f = _sweep_all(P, list(GROUPS), inject=cu + (kind, arg))
     name = arg if kind == "scalar" else kind
     assert f["failed"] == {name: [list(cu)]}, f["failed"]
@@ -104,7 +105,7 @@ def test_injection_fails_exactly_that_cu_and_kind(P, clean, kind, arg):
 
 
 def test_corrupt_expected_fails_that_wave_of_every_record(P):
-    from nanogpu.probe.selftest import mix32
+    from nanogpu.probe.selftest_common import mix32
     from nanogpu.probe.selftest_scalar import EXACT_GROUPS, GROUPS
 
     for i, g in enumerate(EXACT_GROUPS):
@@ -116,7 +117,7 @@ def test_corrupt_expected_fails_that_wave_of_every_record(P):
 
 
 def test_every_word_of_every_table_can_fail_the_sweep(P):
-    from nanogpu.probe.selftest import mix32
+    from nanogpu.probe.selftest_common import mix32
     from nanogpu.probe.selftest_scalar import EXACT_GROUPS
 
     t0 = time.perf_counter()
@@ -132,7 +133,7 @@ def test_every_word_of_every_table_can_fail_the_sweep(P):
 
 def test_every_word_of_the_load_table_can_fail_the_sweep(P):
     """All 4096 words, 512 a call (a sweep takes a fraction of a millisecond); the time is printed."""
-    from nanogpu.probe.selftest import mix32
+    from nanogpu.probe.selftest_common import mix32
 
     t0 = time.perf_counter()
     for first in range(0, 4096, 512):

@@ -44,7 +44,7 @@ def flips_of(name: str) -> list[tuple[int, int]]:
 
 def expected_fields(name: str) -> tuple[int, int, int, int]:
     """(fail bits, lds_bad, failed-path bits, path waves) of every record when `name`'s tile is wrong."""
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     if name == "bf16":
         return (0xF, -1, 0, 0)          # all four waves, no LDS bit, no path
@@ -54,7 +54,7 @@ def expected_fields(name: str) -> tuple[int, int, int, int]:
 @pytest.mark.parametrize("name", TILES)
 def test_every_word_of_the_expected_tile_is_compared_by_all_four_waves(P, name):
     """One unmasked sweep of 1 round, all paths selected, per word of `name`'s tile."""
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     flips = flips_of(name)
     t0 = time.perf_counter()
@@ -105,7 +105,7 @@ def test_plain_cu_sweep_binding_notices_a_word_of_every_register_half_and_parity
 def test_the_python_hook_agrees_with_the_loop_and_a_zero_xor_is_clean(P, name):
     """`cu_sweep_paths(corrupt_expected=...)` on the tile's last word, every record; and the hook
     with nothing to flip reports a clean chip, so it is the flipped bit that fails the check."""
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     last = tile_words(name) - 1
     want = expected_fields(name)
@@ -121,7 +121,7 @@ def test_the_python_hook_agrees_with_the_loop_and_a_zero_xor_is_clean(P, name):
 def test_a_flipped_word_is_restored_before_the_next_flip(P, name):
     """Both uploads of the sweep's session (the bf16 tile; the path tiles), all paths selected: after
     word 5 was flipped, a zero XOR of word 6 is clean on every record only if word 5 was put back."""
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     r = P.sweep_sensitivity(0, name, [(5, 1 << 5), (6, 0), (6, 1 << 6)], list(PATHS), [], 1, SEED)
     fails, clean = (expected_fields(name),) * 2, ((0, -1, 0, 0),) * 2
@@ -129,7 +129,7 @@ def test_a_flipped_word_is_restored_before_the_next_flip(P, name):
 
 
 def test_the_hook_rejects_a_word_beyond_the_tile_and_a_path_not_selected(P):
-    from nanogpu.probe.selftest import PATHS
+    from nanogpu.probe.selftest_paths import PATHS
 
     for bad in (("bf16", 1024, 1), ("f16", 1024, 1), ("f64", 512, 1), ("bf17", 0, 1)):
         with pytest.raises(ValueError):

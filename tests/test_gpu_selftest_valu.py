@@ -97,10 +97,11 @@ def test_clean_sweep_covers_every_cu(P, clean):
                                       ("regs", 0), ("regs", 255), ("regs", 447), ("approx", None)])
 def test_injection_fails_exactly_that_cu_and_kind(P, clean, kind, arg):
     from nanogpu.probe import selftest as S
+    from nanogpu.probe import selftest_common as C
     from nanogpu.probe.selftest_valu import GROUPS
 
     rec = clean[0]["records"][len(clean[0]["records"]) // 3]
-    cu = (rec[0], S.cu_key(rec[1]))
+    cu = (rec[0], C.cu_key(rec[1]))
     inject = cu + ((kind, arg) if arg is not None else (kind,))
     r, f = _sweep_all(P, list(GROUPS), inject=inject)
     name = arg if kind == "valu" else kind
@@ -121,7 +122,7 @@ def test_injection_fails_exactly_that_cu_and_kind(P, clean, kind, arg):
 
 
 def test_corrupt_expected_fails_every_wave_of_every_record(P):
-    from nanogpu.probe.selftest import mix32
+    from nanogpu.probe.selftest_common import mix32
     from nanogpu.probe.selftest_valu import EXACT_GROUPS, GROUPS
 
     for i, g in enumerate(EXACT_GROUPS):
@@ -131,7 +132,7 @@ def test_corrupt_expected_fails_every_wave_of_every_record(P):
 
 
 def test_every_word_of_every_table_can_fail_the_sweep(P):
-    from nanogpu.probe.selftest import mix32
+    from nanogpu.probe.selftest_common import mix32
     from nanogpu.probe.selftest_valu import EXACT_GROUPS
 
     t0 = time.perf_counter()

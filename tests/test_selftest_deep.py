@@ -15,6 +15,7 @@ from nanogpu.agent.plugin import Assignment, NanoGpuPlugin
 from nanogpu.k8s import podutil as pu
 from nanogpu.k8s.fake_apiserver import FakeKubeStore, InProcKube
 from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_common as C
 from nanogpu.topology.model import NodeTopology, synthetic_mi355x
 
 GIB = 1 << 30
@@ -79,7 +80,7 @@ PINS = [((0, 0, 0, 0), 0x00000000), ((0, 3, 0x1234ABCD, 0), 0x00D1E6CC), ((4095,
 
 
 def test_pattern_twin_pins():
-    assert S.mix32(1) == 0x514E28B7                                   # murmur3's finaliser
+    assert C.mix32(1) == 0x514E28B7                                   # murmur3's finaliser
     for args, want in PINS:
         assert S.pattern_word(*args) == want, args
     for i in (0, 77, (1 << 33) + 1):

@@ -1,4 +1,4 @@
-"""The edge tiles of the deep self-test's matrix paths (nanogpu.probe.selftest.edge_tiles): the
+"""The edge tiles of the deep self-test's matrix paths (nanogpu.probe.selftest_paths.edge_tiles): the
 conditions that make them exact and complete, checked on the host. tests/test_gpu_selftest_edges.py
 runs the same tiles through `matrix_tile` on the device."""
 import functools
@@ -7,13 +7,13 @@ import struct
 
 import pytest
 
-from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_paths as SP
 
 NARROW = ("fp8", "bf8", "i8", "mxfp8", "mxfp6", "mxfp4")
 WIDE = ("f16", "f32", "f64")
 WIDE_STRUCT = {"f16": ("<H", "<e"), "f32": ("<I", "<f"), "f64": ("<Q", "<d")}
-NARROW_DECODE = {"fp8": S.decode_e4m3fn, "mxfp8": S.decode_e4m3fn, "bf8": S.decode_e5m2, "mxfp6": S.decode_e2m3,
-                 "mxfp4": S.decode_e2m1}
+NARROW_DECODE = {"fp8": SP.decode_e4m3fn, "mxfp8": SP.decode_e4m3fn, "bf8": SP.decode_e5m2, "mxfp6": SP.decode_e2m3,
+                 "mxfp4": SP.decode_e2m1}
 
 
 def decode(path, code):
@@ -29,7 +29,7 @@ def decode(path, code):
 
 @functools.lru_cache(maxsize=None)
 def tiles(path):
-    return list(S.edge_tiles(path))
+    return list(SP.edge_tiles(path))
 
 
 _TERMS = {}
@@ -44,7 +44,7 @@ def terms(path, a, b):
 
 
 def _terms(path, a, b):
-    dim, K = S.path_dim(path), S.PATH_K[path]
+    dim, K = SP.path_dim(path), SP.PATH_K[path]
     nz_a = [[k for k in range(K) if decode(path, a[r][k]) != 0] for r in range(dim)]
     nz_b = [{k for k in range(K) if decode(path, b[k][c]) != 0} for c in range(dim)]
     return [(r, c, k) for r in range(dim) for c in range(dim) for k in nz_a[r] if k in nz_b[c]]
@@ -52,28 +52,28 @@ def _terms(path, a, b):
 
 def codes_side(path, a, b):
     """0 when A holds the codes under test and B the units, 1 the other way round."""
-    dim, K = S.path_dim(path), S.PATH_K[path]
+    dim, K = SP.path_dim(path), SP.PATH_K[path]
     a_sparse = all(sum(1 for k in range(K) if a[r][k]) == 1 for r in range(dim))
     return 1 if a_sparse else 0
 
 
-@pytest.mark.parametrize("path", S.PATHS)
+@pytest.mark.parametrize("path", SP.PATHS)
 def test_every_accumulator_has_at_most_one_term_and_every_operand_is_finite(path):
-    dim = S.path_dim(path)
+    dim = SP.path_dim(path)
     assert tiles(path)
     for a, b, _sa, _sb, _opsel in tiles(path):
         t = terms(path, a, b)
         assert len({(r, c) for r, c, _k in t}) == len(t)            # no accumulator twice
         assert len(t) > dim * dim // 2                              # and the tile is not empty
-        assert all(S.code_is_finite(path, c) for row in a for c in row)
-        assert all(S.code_is_finite(path, c) for row in b for c in row)
+        assert all(SP.code_is_finite(path, c) for row in a for c in row)
+        assert all(SP.code_is_finite(path, c) for row in b for c in row)
 
 
-@pytest.mark.parametrize("path", S.PATHS)
+@pytest.mark.parametrize("path", SP.PATHS)
 def test_every_code_meets_a_unit_on_both_sides(path):
     """Every finite code of the narrow formats, and the edge codes of f16 / f32 / f64, is a
     factor of some accumulator's one term in A against a unit in B, and in B against a unit in A."""
-    units = set(S.unit_codes(path))
+    units = set(SP.unit_codes(path))
     assert {decode(path, u) for u in units} == ({1, -1, -128} if path == "i8" else {1.0, -1.0})
     seen = [set(), set()]
     units_used = set()
@@ -85,11 +85,11 @@ def test_every_code_meets_a_unit_on_both_sides(path):
             seen[side].add(code)
             units_used.add(unit)
     if path in NARROW:
-        want = {c for c in range(1 << S.PATH_CODE_BITS[path]) if S.code_is_finite(path, c) and decode(path, c) != 0}
+        want = {c for c in range(1 << SP.PATH_CODE_BITS[path]) if SP.code_is_finite(path, c) and decode(path, c) != 0}
         assert len(want) == {"fp8": 252, "mxfp8": 252, "bf8": 246, "i8": 255, "mxfp6": 62, "mxfp4": 14}[path]
     else:
-        ebits, mbits, bias = S.PATH_FORMAT[path]
-        ones, sign = (1 << mbits) - 1, 1 << (S.PATH_CODE_BITS[path] - 1)
+        ebits, mbits, bias = SP.PATH_FORMAT[path]
+        ones, sign = (1 << mbits) - 1, 1 << (SP.PATH_CODE_BITS[path] - 1)
         edge = [1, ones, 1 << mbits, ((1 << ebits) - 2) << mbits | ones, bias << mbits]
         want = {c | s for c in edge for s in (0, sign)}
         assert [decode(path, c) for c in edge[:4]] == {
@@ -102,18 +102,18 @@ def test_every_code_meets_a_unit_on_both_sides(path):
     for side in range(2):
         held = {c for a, b, *_ in tiles(path) if codes_side(path, a, b) == side
                 for row in (a if side == 0 else b) for c in row}
-        assert {0, 0x80 if path == "i8" else 1 << (S.PATH_CODE_BITS[path] - 1)} <= held
+        assert {0, 0x80 if path == "i8" else 1 << (SP.PATH_CODE_BITS[path] - 1)} <= held
 
 
-@pytest.mark.parametrize("path", S.SCALED_PATHS)
+@pytest.mark.parametrize("path", SP.SCALED_PATHS)
 def test_every_scale_multiplies_a_term_in_every_byte_on_both_sides(path):
     """Every E8M0 value 0..254 scales a non-zero term as A's scale and as B's, carried in each of
     the four bytes of the scale register; within a tile scale_a + scale_b - 254 stays in
     [-2, 2] for every (row, col, block), terms or not."""
-    dim = S.path_dim(path)
+    dim = SP.path_dim(path)
     seen = [set(), set()]          # (scale, byte) of A and of B
     for a, b, sa, sb, opsel in tiles(path):
-        lo, hi = S.EDGE_SCALE_SUM
+        lo, hi = SP.EDGE_SCALE_SUM
         assert all(lo <= sa[r][blk] + sb[blk][c] - 254 <= hi for r in range(dim) for c in range(dim) for blk in range(2))
         assert all(0 <= v <= 254 for row in sa + sb for v in row)
         for r, c, k in terms(path, a, b):
@@ -121,30 +121,30 @@ def test_every_scale_multiplies_a_term_in_every_byte_on_both_sides(path):
             seen[1].add((sb[k // 32][c], opsel[1]))
     every = {(s, byte) for s in range(255) for byte in range(4)}
     assert seen[0] == every and seen[1] == every, (sorted(every - seen[0])[:8], sorted(every - seen[1])[:8])
-    assert len(tiles(path)) == S.EDGE_SCALE_TILES
+    assert len(tiles(path)) == SP.EDGE_SCALE_TILES
 
 
 def _smallest_normal(path):
     return 2.0 ** -1022 if path == "f64" else 1 if path == "i8" else 2.0 ** -126
 
 
-@pytest.mark.parametrize("path", S.PATHS)
+@pytest.mark.parametrize("path", SP.PATHS)
 def test_exact_product_is_decode_times_scale_in_every_slot(path):
     """`exact_product` (integers, path_decode) against the formats' decoders in floating point:
     every accumulator is its one term's decode(a) x 2^(sa - 127) x decode(b) x 2^(sb - 127), or
     +0. The result is exactly representable in the accumulator, and normal there. The one
     exception to "normal" is forced: a subnormal of f32 or f64 times +-1 is that subnormal, since
     the operand's format is the accumulator's."""
-    dim = S.path_dim(path)
+    dim = SP.path_dim(path)
     subnormal_in = 0
     for a, b, sa, sb, _opsel in tiles(path):
-        units, abs_units, unit_exp = S.exact_product(path, a, b, sa, sb)
-        values = S.tile_values(path, [u for row in units for u in row], unit_exp)
+        units, abs_units, unit_exp = SP.exact_product(path, a, b, sa, sb)
+        values = SP.tile_values(path, [u for row in units for u in row], unit_exp)
         want = [0] * (dim * dim) if path == "i8" else [0.0] * (dim * dim)
         for r, c, k in terms(path, a, b):
             v = decode(path, a[r][k]) * decode(path, b[k][c])
             if sa is not None:                      # every factor and partial product is exact in a double
-                v = v * S.decode_e8m0(sa[r][k // 32]) * S.decode_e8m0(sb[k // 32][c])
+                v = v * SP.decode_e8m0(sa[r][k // 32]) * SP.decode_e8m0(sb[k // 32][c])
             want[r * dim + c] = v
             assert abs(units[r][c]) == abs_units[r][c] != 0
             if abs(v) < _smallest_normal(path):
@@ -155,9 +155,9 @@ def test_exact_product_is_decode_times_scale_in_every_slot(path):
         assert values == want
         assert all(math.copysign(1.0, v) > 0 for v in values if v == 0)        # no -0 in an expected tile
         # representable: the words decode back to the same values
-        words = S.tile_words(path, values)
+        words = SP.tile_words(path, values)
         if a is tiles(path)[0][0]:
-            assert S.product_words(path, a, b, sa, sb) == words
+            assert SP.product_words(path, a, b, sa, sb) == words
         if path == "i8":
             assert [w - (1 << 32) if w >> 31 else w for w in words] == want
         elif path == "f64":
@@ -169,7 +169,7 @@ def test_exact_product_is_decode_times_scale_in_every_slot(path):
 
 def test_edge_tile_counts():
     """What the GPU test puts on the device: tiles per path (recorded in profiles/gpu_calibration.md)."""
-    assert {p: len(tiles(p)) for p in S.PATHS} == {"f16": 12, "fp8": 4, "bf8": 4, "i8": 4, "mxfp8": 256, "mxfp6": 256,
+    assert {p: len(tiles(p)) for p in SP.PATHS} == {"f16": 12, "fp8": 4, "bf8": 4, "i8": 4, "mxfp8": 256, "mxfp6": 256,
                                                    "mxfp4": 256, "f32": 12, "f64": 12}
 
 
@@ -178,6 +178,6 @@ def test_a_naive_scale_choice_is_rejected_by_the_window():
     the ends only by +-1; scale_b[c] = 254 - scale_a[c] taken per index does not: row 0 against
     column 31 of such a tile has scale sum -31. The builder's sums are in [-1, 1]."""
     for t in (0, 1, 130, 255):
-        sa, sb, _ = S.edge_scales("mxfp8", t)
+        sa, sb, _ = SP.edge_scales("mxfp8", t)
         sums = {sa[r][blk] + sb[blk][c] - 254 for r in range(32) for c in range(32) for blk in range(2)}
         assert sums == {-1, 0, 1}

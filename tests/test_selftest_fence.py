@@ -14,6 +14,7 @@ from nanogpu.agent.plugin import NanoGpuPlugin
 from nanogpu.k8s import podutil as pu
 from nanogpu.k8s.fake_apiserver import FakeKubeStore, InProcKube
 from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_paths as SP
 from nanogpu.topology.model import NodeTopology, describe, from_host_json, synthetic_mi355x
 
 GIB = 1 << 30
@@ -57,7 +58,7 @@ class _MaskProbe:
                 fail |= 0b0001
             rec = (k[0], k[1] << 8, fail, 0xF, -1)
             if paths is not None:
-                pf = sum(1 << S.PATHS.index(p) for x, key, p in self.bad_paths.get(dev, ()) if (x, key) == k and p in paths)
+                pf = sum(1 << SP.PATHS.index(p) for x, key, p in self.bad_paths.get(dev, ()) if (x, key) == k and p in paths)
                 rec += (pf, 0b0001 if pf else 0)
             recs.append(rec)
         return recs
@@ -66,7 +67,7 @@ class _MaskProbe:
         return {"records": self._records(dev, mask, rounds), "lds_bytes": 163840, "ms": 0.25}
 
     def cu_sweep_paths(self, dev, mask, rounds, seed, paths, inject=None):
-        return {"records": self._records(dev, mask, rounds, paths), "paths": list(S.PATHS), "checked": list(paths),
+        return {"records": self._records(dev, mask, rounds, paths), "paths": list(SP.PATHS), "checked": list(paths),
                 "lds_bytes": 163840, "ms": 0.25}
 
     def hbm_pattern_check(self, dev, nbytes, seed, passes=2, corrupt=(), verify_seed=None, cu_mask=None):
@@ -186,7 +187,7 @@ def test_one_bad_cu_gives_exactly_its_unit():
     rep = S.deep_selftest(P, 0, seed=1)
     assert not rep.ok and S.fenceable(rep) and S.failed_cus(rep) == {(3, 17)}
     P.sweeps.clear()
-    loc = S.localise_failure(P, 0, rep, range(32), 8, None, seed=1)
+    loc = S.localise_failure(P, 0, rep, range(32), 8, paths=None, seed=1)
     assert loc.bad_units == [17] and loc.unexplained == []
     assert loc.unit_keys[17] == [(x, 17) for x in range(8)] and sorted(loc.unit_keys) == list(range(32))
     assert [bits for _, bits, _ in P.sweeps] == [_unit_bits(u) for u in range(32)]     # one masked sweep a unit
@@ -195,26 +196,26 @@ def test_one_bad_cu_gives_exactly_its_unit():
 
 def test_two_bad_cus_in_one_unit_give_one_unit_and_a_path_failure_localises_too():
     P = _MaskProbe(bad_cus={0: [(3, 17), (6, 17, S.FAIL_LDS)]})
-    loc = S.localise_failure(P, 0, S.deep_selftest(P, 0, seed=1), range(32), 8, None, seed=1)
+    loc = S.localise_failure(P, 0, S.deep_selftest(P, 0, seed=1), range(32), 8, paths=None, seed=1)
     assert loc.bad_units == [17] and loc.unexplained == []
     P = _MaskProbe(bad_paths={0: [(2, 9, "f16")]})
     assert S.deep_selftest(P, 0, seed=1).ok                       # the plain sweep does not see it
     rep = S.deep_selftest(P, 0, seed=1, paths=["f16", "i8"])
     assert not rep.ok and S.fenceable(rep) and S.failed_cus(rep) == {(2, 9)}
-    loc = S.localise_failure(P, 0, rep, range(32), 8, ["f16", "i8"], seed=1)
+    loc = S.localise_failure(P, 0, rep, range(32), 8, paths=["f16", "i8"], seed=1)
     assert loc.bad_units == [9] and loc.unexplained == []
-    assert S.localise_failure(P, 0, rep, range(32), 8, ["i8"], seed=1).bad_units == []   # the same paths, or nothing
+    assert S.localise_failure(P, 0, rep, range(32), 8, paths=["i8"], seed=1).bad_units == []   # the same paths, or nothing
 
 
 def test_a_flaky_cu_gives_no_bad_unit_and_stays_unexplained():
     P = _MaskProbe(flaky={0: [(3, 17)]})
     rep = S.deep_selftest(P, 0, seed=1)
     assert not rep.ok
-    loc = S.localise_failure(P, 0, rep, range(32), 8, None, seed=1)
+    loc = S.localise_failure(P, 0, rep, range(32), 8, paths=None, seed=1)
     assert loc.bad_units == [] and loc.unexplained == [(3, 17)]
     # a bad unit explains only its own CUs: a second failing CU outside the candidates stays unexplained
     P = _MaskProbe(bad_cus={0: [(3, 17), (1, 2)]})
-    loc = S.localise_failure(P, 0, S.deep_selftest(P, 0, seed=1), range(8, 32), 8, None, seed=1)
+    loc = S.localise_failure(P, 0, S.deep_selftest(P, 0, seed=1), range(8, 32), 8, paths=None, seed=1)
     assert loc.bad_units == [17] and loc.unexplained == [(1, 2)]
 
 

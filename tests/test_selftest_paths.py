@@ -16,6 +16,8 @@ from nanogpu.agent.node import NodeAgent, build_parser
 from nanogpu.k8s import podutil as pu
 from nanogpu.k8s.fake_apiserver import FakeKubeStore, InProcKube
 from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_common as C
+from nanogpu.probe import selftest_paths as SP
 from nanogpu.topology.model import synthetic_mi355x
 
 GIB = 1 << 30
@@ -23,7 +25,7 @@ ALL = [(x, k) for x in range(8) for k in range(32)]
 
 
 # ----------------------------------------------------------------------------- decoders
-@pytest.mark.parametrize("dtype,decode", [("float8_e4m3fn", S.decode_e4m3fn), ("float8_e5m2", S.decode_e5m2)])
+@pytest.mark.parametrize("dtype,decode", [("float8_e4m3fn", SP.decode_e4m3fn), ("float8_e5m2", SP.decode_e5m2)])
 def test_fp8_decoders_agree_with_torch_on_every_code(dtype, decode):
     import torch
 
@@ -37,23 +39,23 @@ def test_fp8_decoders_agree_with_torch_on_every_code(dtype, decode):
         checked += 1
         assert got == want[c] and math.copysign(1, got) == math.copysign(1, want[c]), (c, got, want[c])
     assert checked == (254 if dtype == "float8_e4m3fn" else 250)
-    assert S.decode_e4m3fn(0x7E) == 448.0 and S.decode_e5m2(0x7B) == 57344.0
+    assert SP.decode_e4m3fn(0x7E) == 448.0 and SP.decode_e5m2(0x7B) == 57344.0
 
 
 def test_small_format_decoders_against_their_tables():
     e2m1 = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0]
-    assert [S.decode_e2m1(c) for c in range(16)] == e2m1 + [-v for v in e2m1]
-    assert math.copysign(1, S.decode_e2m1(8)) == -1
+    assert [SP.decode_e2m1(c) for c in range(16)] == e2m1 + [-v for v in e2m1]
+    assert math.copysign(1, SP.decode_e2m1(8)) == -1
     e2m3 = [0.0, 0.125, 0.25, 0.375, 0.5, 0.625, 0.75, 0.875,          # subnormal: m / 8
             1.0, 1.125, 1.25, 1.375, 1.5, 1.625, 1.75, 1.875,
             2.0, 2.25, 2.5, 2.75, 3.0, 3.25, 3.5, 3.75,
             4.0, 4.5, 5.0, 5.5, 6.0, 6.5, 7.0, 7.5]
-    assert [S.decode_e2m3(c) for c in range(64)] == e2m3 + [-v for v in e2m3]
-    assert {c: S.decode_e8m0(c) for c in (0, 120, 126, 127, 128, 129, 254)} == {
+    assert [SP.decode_e2m3(c) for c in range(64)] == e2m3 + [-v for v in e2m3]
+    assert {c: SP.decode_e8m0(c) for c in (0, 120, 126, 127, 128, 129, 254)} == {
         0: 2.0 ** -127, 120: 1 / 128, 126: 0.5, 127: 1.0, 128: 2.0, 129: 4.0, 254: 2.0 ** 127}
-    assert math.isnan(S.decode_e8m0(255))
-    assert S.path_decode("i8", 0x80) == (-128, 0) and S.path_decode("i8", 0x7F) == (127, 0)
-    assert S.path_decode("f16", 0x3C00) == (1 << 10, -10) and S.path_decode("f32", 0x3F800000) == (1 << 23, -23)
+    assert math.isnan(SP.decode_e8m0(255))
+    assert SP.path_decode("i8", 0x80) == (-128, 0) and SP.path_decode("i8", 0x7F) == (127, 0)
+    assert SP.path_decode("f16", 0x3C00) == (1 << 10, -10) and SP.path_decode("f32", 0x3F800000) == (1 << 23, -23)
 
 
 # ----------------------------------------------------------------------------- host program and twin
@@ -61,9 +63,9 @@ def test_small_format_decoders_against_their_tables():
 def twin():
     """Every path's expected tile from the Python twin, computed once."""
     out = {}
-    for p in S.PATHS:
-        t = S.path_expected(p)
-        t["checksum"] = S.tile_checksum(S.tile_words(p, S.tile_values(p, t["units"], t["unit_exp"])))
+    for p in SP.PATHS:
+        t = SP.path_expected(p)
+        t["checksum"] = C.tile_checksum(SP.tile_words(p, SP.tile_values(p, t["units"], t["unit_exp"])))
         out[p] = t
     return out
 
@@ -79,35 +81,35 @@ def test_host_program_agrees_with_the_twin(kind, twin):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     host = json.loads(r.stdout)
-    assert list(host) == list(S.PATHS)
-    for p in S.PATHS:
+    assert list(host) == list(SP.PATHS)
+    for p in SP.PATHS:
         assert host[p]["checksum"] == twin[p]["checksum"], p
         assert host[p]["unit_exp"] == twin[p]["unit_exp"] and host[p]["sum_abs_max"] == twin[p]["sum_abs_max"], p
 
 
-@pytest.mark.parametrize("path", S.PATHS)
+@pytest.mark.parametrize("path", SP.PATHS)
 def test_twin_exactness_bound_and_coverage(path, twin):
     t = twin[path]
     limit = {"i8": 31, "f64": 53}.get(path, 24)
     assert t["limit_bits"] == limit and t["exact"] and 0 < t["sum_abs_max"] < 1 << limit
-    assert len(t["units"]) == S.path_dim(path) ** 2 and len(set(t["units"])) > 1
+    assert len(t["units"]) == SP.path_dim(path) ** 2 and len(set(t["units"])) > 1
     assert all(abs(u) <= t["sum_abs_max"] for u in t["units"])
-    assert S.path_coverage(path) == []
+    assert SP.path_coverage(path) == []
 
 
 def test_generators_pack_codes_as_the_kernel_holds_them():
-    row = S.path_codes("mxfp6", 0, 3, 7)
-    packed = S.path_dword("mxfp6", 0, 3, 7, 0) | S.path_dword("mxfp6", 0, 3, 7, 1) << 32
+    row = SP.path_codes("mxfp6", 0, 3, 7)
+    packed = SP.path_dword("mxfp6", 0, 3, 7, 0) | SP.path_dword("mxfp6", 0, 3, 7, 1) << 32
     assert len(row) == 64 and row[5] == (packed >> 30) & 0x3F                 # code 5 straddles two dwords
-    assert all(5 <= (c >> 3) & 0xF <= 8 for c in S.path_codes("fp8", 1, 2, 9))
-    assert all(14 <= (c >> 2) & 0x1F <= 17 for c in S.path_codes("bf8", 0, 6, 31))
-    assert (S.path_codes("f16", 0, 0, 2)[0] >> 10) & 0x1F == 16 and S.path_codes("f16", 0, 1, 2)[0] == 0
-    assert S.path_codes("f32", 1, 0, 9)[0] & 0x7FFFFFFF == 0x3F800000
-    assert {S.path_opsel(op, s) for op in range(2) for s in range(S.PATH_STEPS)} == {0, 1, 2, 3}
-    assert S.parse_paths("all") == list(S.PATHS) and S.parse_paths("mxfp4, fp8") == ["fp8", "mxfp4"]
-    assert S.parse_paths(None) == S.parse_paths("") == S.parse_paths([]) == []
+    assert all(5 <= (c >> 3) & 0xF <= 8 for c in SP.path_codes("fp8", 1, 2, 9))
+    assert all(14 <= (c >> 2) & 0x1F <= 17 for c in SP.path_codes("bf8", 0, 6, 31))
+    assert (SP.path_codes("f16", 0, 0, 2)[0] >> 10) & 0x1F == 16 and SP.path_codes("f16", 0, 1, 2)[0] == 0
+    assert SP.path_codes("f32", 1, 0, 9)[0] & 0x7FFFFFFF == 0x3F800000
+    assert {SP.path_opsel(op, s) for op in range(2) for s in range(SP.PATH_STEPS)} == {0, 1, 2, 3}
+    assert SP.parse_paths("all") == list(SP.PATHS) and SP.parse_paths("mxfp4, fp8") == ["fp8", "mxfp4"]
+    assert SP.parse_paths(None) == SP.parse_paths("") == SP.parse_paths([]) == []
     with pytest.raises(ValueError):
-        S.parse_paths("fp8,fp9")
+        SP.parse_paths("fp8,fp9")
 
 
 # ----------------------------------------------------------------------------- fold_paths
@@ -120,15 +122,15 @@ def _records(keys, path_fail=0, waves=0):
 
 
 def test_fold_paths_keeps_a_failure_across_a_clean_revisit():
-    fp8, mxfp4 = 1 << S.PATHS.index("fp8"), 1 << S.PATHS.index("mxfp4")
+    fp8, mxfp4 = 1 << SP.PATHS.index("fp8"), 1 << SP.PATHS.index("mxfp4")
     seen = [c for c in ALL if c != (6, 9)]
     recs = _records(seen) + _records([(3, 17)], fp8 | mxfp4, 0b0100) + _records(seen)   # two visits; one of (3,17)'s three fails
-    rep = S.fold_paths(recs, S.PATHS, ALL)
+    rep = SP.fold_paths(recs, SP.PATHS, ALL)
     assert rep["failed"] == {"fp8": [[3, 17]], "mxfp4": [[3, 17]]}
     assert rep["cus"] == [{"xcc": 3, "cu_key": 17, "paths": ["fp8", "mxfp4"], "waves": 0b0100}]
     assert rep["uncovered"] == [[6, 9]] and rep["cus_uncovered"] == 1           # not a failure
     assert rep["cus_seen"] == 255 and rep["cus_expected"] == 256
-    clean = S.fold_paths(_records(ALL), S.PATHS, 256)
+    clean = SP.fold_paths(_records(ALL), SP.PATHS, 256)
     assert clean["failed"] == {} and clean["cus"] == [] and clean["cus_uncovered"] == 0
 
 
@@ -163,8 +165,8 @@ class _FakePathProbe:
         recs = _records(self._keys(mask))
         for x, k, name in self.bad_paths.get(dev, ()):
             if name in paths:
-                recs += _records([(x, k)], 1 << S.PATHS.index(name), 0b0001)
-        return {"records": recs, "paths": list(S.PATHS), "checked": list(paths), "lds_bytes": 163840, "ms": 0.25}
+                recs += _records([(x, k)], 1 << SP.PATHS.index(name), 0b0001)
+        return {"records": recs, "paths": list(SP.PATHS), "checked": list(paths), "lds_bytes": 163840, "ms": 0.25}
 
     def hbm_pattern_check(self, dev, nbytes, seed, passes=2, corrupt=(), verify_seed=None):
         self.hbm_calls.append((dev, nbytes))
@@ -179,8 +181,8 @@ class _NoPathProbe(_FakePathProbe):
 def test_deep_selftest_with_all_paths():
     P = _FakePathProbe()
     rep = S.deep_selftest(P, 0, paths="all", seed=1)
-    assert rep.ok and rep.paths == {"checked": list(S.PATHS), "failed": {}}
-    assert P.sweeps == [] and [s[3] for s in P.path_sweeps] == [list(S.PATHS)]     # one visit per CU, not two
+    assert rep.ok and rep.paths == {"checked": list(SP.PATHS), "failed": {}}
+    assert P.sweeps == [] and [s[3] for s in P.path_sweeps] == [list(SP.PATHS)]     # one visit per CU, not two
     assert rep.sweep["cus_seen"] == 256 and rep.sweep["launches"] == 1
     bad = _FakePathProbe(bad_paths={0: [(3, 17, "mxfp6")]})
     rep = S.deep_selftest(bad, 0, paths="all", seed=1)
@@ -188,7 +190,7 @@ def test_deep_selftest_with_all_paths():
     assert "mxfp6" in rep.describe_failure() and "xcc 3" in rep.describe_failure()
     assert S.deep_selftest(bad, 0, paths=["fp8", "f64"], seed=1).ok                 # the bad path is not asked for
     assert bad.path_sweeps[-1][3] == ["fp8", "f64"]
-    assert rep.to_dict()["paths"]["checked"] == list(S.PATHS)
+    assert rep.to_dict()["paths"]["checked"] == list(SP.PATHS)
 
 
 def test_deep_selftest_without_paths_never_calls_the_path_sweep():
@@ -226,7 +228,7 @@ def test_flag_parses_implies_deep_and_rejects_unknown_names(capsys):
     ap = build_parser()
     a = ap.parse_args(["--node-name", "n", "--selftest-paths", "fp8,mxfp4"])
     assert a.selftest and a.selftest_deep and a.selftest_paths == ["fp8", "mxfp4"]
-    assert ap.parse_args(["--selftest-paths", "all"]).selftest_paths == list(S.PATHS)
+    assert ap.parse_args(["--selftest-paths", "all"]).selftest_paths == list(SP.PATHS)
     a = ap.parse_args(["--node-name", "n", "--selftest-deep"])
     assert a.selftest_deep and a.selftest_paths == []                            # the default is off
     for bad in ("fp8,fp9", "", "bf16"):
@@ -235,7 +237,7 @@ def test_flag_parses_implies_deep_and_rejects_unknown_names(capsys):
         assert e.value.code == 2
     assert "unknown matrix path" in capsys.readouterr().err
     assert NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False, selftest_paths="fp8").selftest_deep
-    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_paths
+    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_parts.paths
 
 
 def test_a_failing_path_makes_the_device_unhealthy_at_startup_and_periodically():

@@ -14,6 +14,7 @@ from nanogpu.agent.node import NodeAgent, build_parser
 from nanogpu.k8s import podutil as pu
 from nanogpu.k8s.fake_apiserver import FakeKubeStore, InProcKube
 from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_common as C
 from nanogpu.probe import selftest_scalar as V
 from nanogpu.topology.model import synthetic_mi355x
 
@@ -144,7 +145,7 @@ def test_spot_values_by_hand_logic_bits_cmp():
 def test_spot_values_by_hand_vcc_fold_operand_and_patterns():
     # fold: rotl(h ^ d, 7) + c + 0x9e3779b9
     assert V.fold(0, 0, 0) == 0x9E3779B9 and V.fold(1, 0, 1) == 0x9E3779B9 + 129
-    assert V.operand("add", 0, 0, 0) == S.mix32(0x5CA1A2B3) and V.operand("mul", 1, 2, 3) == S.mix32(0x5CA1A2B3 ^ 1 << 24 ^ 1 << 16 ^ 2 << 8 ^ 3)
+    assert V.operand("add", 0, 0, 0) == C.mix32(0x5CA1A2B3) and V.operand("mul", 1, 2, 3) == C.mix32(0x5CA1A2B3 ^ 1 << 24 ^ 1 << 16 ^ 2 << 8 ^ 3)
     # vcc with thr = 0: no lane is below, mask = 0, count 0, the search finds the guard bit 63; m = 0: w = v ^ k with
     # k = 0 is v, never below 0, so mask2 = 0: the word folds (0, 0), (0, 63), v0 ^ h, (0, 0), (0, 0)
     h0, u0 = 0x1234, 0x77
@@ -156,7 +157,7 @@ def test_spot_values_by_hand_vcc_fold_operand_and_patterns():
     assert V.vcc_step(h0, u0, M32, 0, 0) == V.fold(V.fold(h, 0, 0), 0, 0)
     assert V.sreg_word(0, 1) == 0x9E3779B1 ^ 0x7F4A7C15 and V.sreg_word(3, 77, 1) == V.sreg_word(3, 77) ^ M32
     assert V.sreg_word(87, 2) == ((2 * (0x9E3779B1 + 174)) & M32) ^ ((0x7F4A7C15 + 87 * 0x01000193) & M32)
-    assert V.smem_word(5) == S.mix32(5 ^ V.SMEM_SALT)
+    assert V.smem_word(5) == C.mix32(5 ^ V.SMEM_SALT)
 
 
 def test_parse_scalar():
@@ -381,8 +382,8 @@ def test_flag_parses_and_implies_deep(capsys):
         assert e.value.code == 2
     assert "unknown scalar group" in capsys.readouterr().err
     agent = NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False, selftest_scalar="sregs")
-    assert agent.selftest_deep and agent.selftest_scalar == ["sregs"]
-    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_scalar
+    assert agent.selftest_deep and agent.selftest_parts.scalar == ["sregs"]
+    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_parts.scalar
 
 
 def test_agent_marks_the_device_unhealthy_and_renders_the_metric():

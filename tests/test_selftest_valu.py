@@ -14,6 +14,7 @@ from nanogpu.agent.node import NodeAgent, build_parser
 from nanogpu.k8s import podutil as pu
 from nanogpu.k8s.fake_apiserver import FakeKubeStore, InProcKube
 from nanogpu.probe import selftest as S
+from nanogpu.probe import selftest_common as C
 from nanogpu.probe import selftest_valu as V
 from nanogpu.topology.model import synthetic_mi355x
 
@@ -91,7 +92,7 @@ def test_spot_values_by_hand():
     assert V.round_rne(V.Fraction(0x40000040), V.F32, c)[0] == 0x4E800000           # 31 bits, tie to even
     assert V.ordered_key(0x3F800000) == 0xBF800000 and V.ordered_key(0x80000000) + 1 == V.ordered_key(0)
     assert c.abnormal == 0
-    assert V.operand("fma32", 0, 0, 0) == S.mix32(0x5A17C0DE) and V.f32_win(0xFFFFFFFF, -3) == 0xBE7FFFFF
+    assert V.operand("fma32", 0, 0, 0) == C.mix32(0x5A17C0DE) and V.f32_win(0xFFFFFFFF, -3) == 0xBE7FFFFF
 
 
 def test_spot_values_by_hand_of_the_other_groups():
@@ -189,7 +190,7 @@ def test_fold_regs_reports_first_slot_and_lane():
 
 
 def test_fold_approx_majority():
-    one = [r for r in _clean() if (r[0], S.cu_key(r[1])) != (7, 31)] + [_rec(7, 31, ahash=HASH ^ 4)]
+    one = [r for r in _clean() if (r[0], C.cu_key(r[1])) != (7, 31)] + [_rec(7, 31, ahash=HASH ^ 4)]
     assert V.fold_valu(one, V.GROUPS, 256)["failed"] == {"approx": [[7, 31]]}       # a minority of 1 in 256
     eight = [(x, 0) for x in range(8)]
     tie = [_rec(x, 0, ahash=HASH ^ (x & 1)) for x, _ in eight]
@@ -371,7 +372,7 @@ def test_flag_parses_and_implies_deep(capsys):
         assert e.value.code == 2
     assert "unknown vector-ALU group" in capsys.readouterr().err
     assert NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False, selftest_valu="regs").selftest_deep
-    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_valu
+    assert not NodeAgent(None, "n", synthetic_mi355x(1), device_plugin=False).selftest_parts.valu
 
 
 def test_agent_marks_the_device_unhealthy_and_renders_the_metric():
