@@ -162,6 +162,11 @@ class Frontend {
   std::atomic<uint64_t> bind_handoffs{0}, pods_published{0};
   // binds whose pod another worker had not published yet when they came (they waited for it)
   std::atomic<uint64_t> handoff_waits{0};
+  // priorities answers computed in the spin window behind their pod's filter answer, how many of
+  // them the priorities request then took as they were, and how many it found out of date
+  std::atomic<uint64_t> prio_prepared{0}, prio_prepared_used{0}, prio_prepared_stale{0};
+  // plan-memo entries of a node just nominated or reserved on re-evaluated ahead of the next filter
+  std::atomic<uint64_t> memo_ahead{0};
   static constexpr uint64_t kHandoffWaitNs = 200'000;
   static constexpr uint64_t kDeferredNominationWaitNs = 100'000;
   std::atomic<uint64_t> loop_max_ns{0};   // longest event-batch a worker spent between epoll_waits
@@ -212,6 +217,20 @@ class Frontend {
   // priorities right behind its pod's filter, nothing changed since: the filter's placements
   bool reuse_assume(VerbScratch& s, std::string_view uid, const Demand& dem, const std::vector<int32_t>& ids,
                     std::vector<int32_t>* rcs, std::vector<int32_t>* scores);
+  // The priorities answer over `ids` (names: their request tokens) written to *out: the
+  // placements (the filter's when still good), the tie-break, the lead, normalisation. Returns
+  // the node id the caller nominates for the pod, -1: none. `reuse_only`: from the filter's
+  // placements or not at all (-2, nothing written): the answer prepared ahead of its request.
+  struct NameToks;
+  int32_t priorities_answer(VerbScratch& s, std::string_view uid, const Demand& dem, const std::vector<int32_t>& ids,
+                            const NameToks& names, bool reuse_only, std::string* out);
+  // the nomination priorities_answer asked for: after the answer on a worker, else now
+  void nominate_for_priorities(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem);
+  // run_deferred: the answer of the priorities request that follows the filter just answered
+  void prepare_priorities(VerbScratch& s);
+  // one remembered demand class evaluated on the node a nomination / reservation just changed
+  // (the busy poll calls it between its probes); false: nothing left to do
+  bool memo_ahead_step(VerbScratch& s);
   void note_bind_wall(uint64_t ns);
   // a response for connection `conn` of worker w, on w's thread: sent, then its next request
   struct Reply;
@@ -233,6 +252,9 @@ class Frontend {
   std::atomic<bool> spin_nap_{false};
   std::atomic<bool> spin_recv_{false};
   std::atomic<bool> spin_recv_binds_{false};
+  // NANOGPU_FE_PREPARE (read once): unset / 1 both, 0 neither, a / b one of them
+  bool prepare_prio_ = true;    // a: priorities answers prepared behind their filter's answer
+  bool memo_ahead_ = true;      // b: plan memos re-validated ahead of the next filter
   std::vector<std::unique_ptr<Worker>> workers_;
 
   // this instance among every Frontend the process made: thread_local caches (the verbs'

@@ -51,6 +51,8 @@ enum IoKind : int {
   kLedgerMemoCold,
   kLedgerRingGap,
   kLedgerRevalUndecided,
+  kFePrepare,       // off the cycle's path: a priorities answer prepared behind its filter's answer
+  kFeMemoAhead,     // off the cycle's path: one demand class re-validated on a node just nominated / reserved on
   kIoKinds
 };
 
@@ -60,7 +62,7 @@ inline const char* io_kind_name(int k) {
       "fe_submit", "fe_parse_bind", "fe_verb", "fe_verb_pod", "fe_verb_names", "fe_verb_cache",
       "fe_verb_assume", "fe_verb_nominate", "ledger_choose", "ledger_cache_hit", "wr_wait", "wr_efd_read", "wr_send", "wr_recv",
       "wr_build", "wr_commit", "pw_recv", "pw_filter", "fe_spin_recv", "ledger_revalidate", "ledger_scan",
-      "ledger_memo_cold", "ledger_ring_gap", "ledger_reval_undecided"};
+      "ledger_memo_cold", "ledger_ring_gap", "ledger_reval_undecided", "fe_prepare", "fe_memo_ahead"};
   return k >= 0 && k < kIoKinds ? names[k] : "?";
 }
 
@@ -81,12 +83,17 @@ struct IoTally {
 };
 
 inline IoTally g_io;
+// Set by a thread around work whose inner sites are not to be tallied (the plan-memo
+// re-validation a worker does ahead of the filters is timed whole, under its own kind: the
+// ledger's kinds keep counting what the verbs themselves pay). Read only while the tally is on.
+inline thread_local bool t_io_quiet = false;
+inline bool io_on() { return g_io.on.load(std::memory_order_relaxed) && !t_io_quiet; }
 
 // RAII: times the enclosing scope into kind k when the tally is on
 struct IoTimer {
   int k;
   uint64_t t0;
-  explicit IoTimer(int kind) : k(kind), t0(g_io.on.load(std::memory_order_relaxed) ? __rdtsc() : 0) {}
+  explicit IoTimer(int kind) : k(kind), t0(io_on() ? __rdtsc() : 0) {}
   ~IoTimer() {
     if (t0) g_io.add(k, __rdtsc() - t0);
   }
@@ -95,13 +102,13 @@ struct IoTimer {
 };
 
 // the same by hand, where the kind is known only afterwards
-inline uint64_t io_t0() { return g_io.on.load(std::memory_order_relaxed) ? __rdtsc() : 0; }
+inline uint64_t io_t0() { return io_on() ? __rdtsc() : 0; }
 inline void io_end(int k, uint64_t t0) {
   if (t0) g_io.add(k, __rdtsc() - t0);
 }
 // an event counted, not timed
 inline void io_count(int k) {
-  if (g_io.on.load(std::memory_order_relaxed)) g_io.add(k, 0);
+  if (io_on()) g_io.add(k, 0);
 }
 
 // ns per TSC tick (calibrated by the front door; 0 when the TSC is not invariant)

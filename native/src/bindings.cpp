@@ -973,6 +973,10 @@ PYBIND11_MODULE(_native, m) {
         d["bind_handoffs"] = f.bind_handoffs.load();
         d["pods_published"] = f.pods_published.load();
         d["handoff_waits"] = f.handoff_waits.load();
+        d["prio_prepared"] = f.prio_prepared.load();
+        d["prio_prepared_used"] = f.prio_prepared_used.load();
+        d["prio_prepared_stale"] = f.prio_prepared_stale.load();
+        d["memo_ahead"] = f.memo_ahead.load();
         py::list ph;
         for (const auto& x : f.phase_max_ns) ph.append(static_cast<double>(x.load()) * 1e-9);
         d["phase_max_s"] = ph;

@@ -574,8 +574,8 @@ struct IdCache {
   // way a compact escape-free list is written. Once nodes fill up, the answer is a subset of the
   // request's window, so without this every priorities call would scan and resolve its whole
   // list again (6 us at 420 nodes).
-  void remember_subset(int src, const std::vector<int32_t>& rcs) {
-    if (src < 0 || !valid[src] || tok[src].size() != rcs.size()) return;
+  int remember_subset(int src, const std::vector<int32_t>& rcs) {   // the subset's slot, -1: none kept
+    if (src < 0 || !valid[src] || tok[src].size() != rcs.size()) return -1;
     int k = src == 0 ? 1 : 0;
     for (int j = 0; j < kListSlots; ++j)
       if (j != src && used[j] < used[k]) k = j;
@@ -599,6 +599,7 @@ struct IdCache {
     epoch[k] = epoch[src];
     used[k] = ++clock;
     mru = k;   // the next request is this pod's priorities
+    return k;
   }
 };
 }  // namespace
@@ -648,6 +649,58 @@ struct Frontend::VerbScratch {
   } last_assume;
   int32_t defer_node = -1;
   Demand defer_dem{};
+  // The priorities answer of the pod whose filter was just answered, computed in the spin window
+  // behind that answer (Frontend::prepare_priorities): everything it is made of is known then.
+  // The request takes it only if all it depends on still reads the same; one use.
+  bool prepare = false;        // this worker prepares (Frontend::prepare_prio_, workers only)
+  bool prep_want = false;      // the last filter left a priorities call to prepare ...
+  int prep_slot = -1;          // ... over this list slot (-1: the fitting subset run_deferred remembers)
+  Demand prep_dem{};           // ... for this demand (the learned-owner flag folded in)
+  struct Prepared {
+    bool valid = false;
+    std::string body, uid;
+    int32_t node = -1;         // the node the answer nominates (-1: none)
+    int slot = -1;
+    uint64_t used = 0, dem_hash = 0, opt_seen = 0, epoch = 0, nom_made = 0;
+    int32_t margin = 0;
+  } prep;
+  // The demand classes this worker's filters evaluated last (a ring), and the node a nomination
+  // or a fresh reservation just changed: the busy poll evaluates each class on it between its
+  // probes (Frontend::memo_ahead_step), so the next filter finds its plan memo current.
+  static constexpr int kClasses = 16;
+  bool ahead = false;          // Frontend::memo_ahead_, workers only
+  struct Class {
+    uint64_t dem_hash = 0, opt_seen = 0;
+    Demand dem{};
+  } classes[kClasses];
+  int n_classes = 0, class_next = 0;
+  int32_t ahead_node = -1;     // -1: nothing pending
+  int ahead_at = 0;            // the next class to evaluate on it
+  void remember_class(const Demand& dem, uint64_t dem_hash) {
+    for (int k = 0; k < n_classes; ++k)
+      if (classes[k].dem_hash == dem_hash && classes[k].opt_seen == opt_seen) return;
+    Class& c = classes[class_next];
+    class_next = (class_next + 1) % kClasses;
+    n_classes = std::min(n_classes + 1, kClasses);
+    c.dem_hash = dem_hash;
+    c.opt_seen = opt_seen;
+    c.dem = dem;
+  }
+  void node_changed(int32_t node) {
+    if (!ahead || n_classes == 0) return;
+    ahead_node = node;
+    ahead_at = 0;
+  }
+};
+
+// a list's names as its request tokens: offsets into the list's text, or views of their own
+struct Frontend::NameToks {
+  std::string_view text;
+  const std::vector<std::pair<uint32_t, uint32_t>>* toks = nullptr;
+  const std::vector<std::string_view>* nraw = nullptr;
+  std::string_view raw_at(size_t i) const {
+    return toks ? text.substr((*toks)[i].first, (*toks)[i].second) : (*nraw)[i];
+  }
 };
 
 // ------------------------------------------------------------------------------ plumbing
@@ -737,6 +790,13 @@ Frontend::Frontend(std::shared_ptr<Ledger> ledger, const std::string& host, int 
   presize_fd_table();
   if (threads < 1) threads = 1;
   if (threads > 64) threads = 64;
+  // NANOGPU_FE_PREPARE: both arms of an A/B are one build. Unset or 1: priorities answers are
+  // prepared and plan memos re-validated in the workers' spin windows; 0: neither; a / b: one
+  if (const char* p = std::getenv("NANOGPU_FE_PREPARE")) {
+    const std::string_view v(p);
+    prepare_prio_ = v == "1" || v == "a" || v.empty();
+    memo_ahead_ = v == "1" || v == "b" || v.empty();
+  }
   py_efd_ = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC);
   if (py_efd_ < 0) throw std::runtime_error("eventfd failed");
   sockaddr_in addr{};
@@ -754,6 +814,8 @@ Frontend::Frontend(std::shared_ptr<Ledger> ledger, const std::string& host, int 
     const char* nd = std::getenv("NANOGPU_FE_NO_DEFER");
     w->scratch.defer = !(nd && nd[0] == '1');
     w->scratch.defer_cache = w->scratch.defer && threads == 1;
+    w->scratch.prepare = prepare_prio_ && w->scratch.defer;
+    w->scratch.ahead = memo_ahead_;
     w->idx = i;
     w->lfd = socket(AF_INET, SOCK_STREAM | SOCK_NONBLOCK | SOCK_CLOEXEC, 0);
     int one = 1;
@@ -1105,7 +1167,11 @@ void Frontend::prepare_bind(std::string_view body, PyRequest* r, VerbScratch& s)
   Plan plan;
   std::memset(&plan, 0, sizeof(plan));
   PreparedBind& b = r->bind;
+  const uint64_t epoch0 = s.ahead ? ledger_->epoch() : 0;
   b.rc = ledger_->reserve(id, uid, pod.demand, o, &plan);
+  // a pod with no nomination to adopt took devices just now (an adoption changes none, and
+  // leaves the epoch alone): the node's plan memos are re-validated ahead of the next filter
+  if (s.ahead && b.rc == kOk && ledger_->epoch() != epoch0) s.node_changed(id);
   if ((b.rc == kOk || b.rc == kOkExisting) && pod.owner) ledger_->set_pod_owner(uid, pod.owner);
   bind_stats.observe(fast_ns() - t0);
   b.ok = true;
@@ -1179,6 +1245,15 @@ void Frontend::run(Worker* w) {
         bio->pump();
         drain_local(w);
       }
+      if (w->mb_pending.load(std::memory_order_acquire)) drain_mailbox();
+      continue;
+    }
+    // Nothing there yet: the window is spent on one demand class of a pending plan-memo
+    // re-validation, then the probe again, so a request never waits longer than one class's
+    // evaluation. Only while busy polling: a worker that sleeps between requests has no idle
+    // window to spend.
+    if (polling && !nap && w->scratch.ahead_node >= 0 && memo_ahead_step(w->scratch) &&
+        spin_recv_.load(std::memory_order_relaxed) && !bind_first_.load(std::memory_order_relaxed)) {
       if (w->mb_pending.load(std::memory_order_acquire)) drain_mailbox();
       continue;
     }
@@ -1668,23 +1743,96 @@ bool Frontend::reuse_assume(VerbScratch& s, std::string_view uid, const Demand& 
 }
 
 void Frontend::run_deferred(VerbScratch& s) {
+  int subset = -1;
   if (s.defer_list >= 0) {
     IoTimer it{kFeVerbNames};
-    s.idc.remember_subset(s.defer_list, s.rcs);
+    subset = s.idc.remember_subset(s.defer_list, s.rcs);
     s.defer_list = -1;
   }
-  if (!s.defer_put && !s.defer_nominate) return;
   const LastPod& last = s.last;
   if (s.defer_put) {
     IoTimer it{kFeVerbCache};
     cache_pod(s, last.uid, last.cached, last.raw, s.defer_dem);
   }
   if (s.defer_nominate) {
-    IoTimer it{kFeVerbNominate};
-    ledger_->nominate(s.defer_node, last.uid, s.defer_dem, s.opt);
-    ledger_->deferred_nomination_end();
+    {
+      IoTimer it{kFeVerbNominate};
+      ledger_->nominate(s.defer_node, last.uid, s.defer_dem, s.opt);
+      ledger_->deferred_nomination_end();
+    }
+    s.node_changed(s.defer_node);   // its plan memos: re-validated before the next filter asks
   }
   s.defer_put = s.defer_nominate = false;
+  if (s.prep_want) {
+    s.prep_want = false;
+    if (s.prep_slot < 0) s.prep_slot = subset;
+    if (s.prep_slot >= 0) {
+      IoTimer it{kFePrepare};
+      prepare_priorities(s);
+    }
+  }
+}
+
+void Frontend::prepare_priorities(VerbScratch& s) {
+  // what kube-scheduler's priorities call for the pod just filtered will carry: the same pod,
+  // the filter's list or its fitting subset, and (nothing having changed) the filter's placements
+  VerbScratch::Prepared& p = s.prep;
+  const IdCache& idc = s.idc;
+  const int slot = s.prep_slot;
+  const LastPod& last = s.last;
+  if (!last.valid || !idc.valid[slot] || !s.last_assume.valid) return;
+  const std::vector<int32_t>& ids = idc.ids[slot];
+  NameToks names;
+  names.text = idc.text[slot];
+  names.toks = &idc.tok[slot];
+  // read before the placements are: a change after this point shows in the key, one before it
+  // in the placements' own epoch check
+  p.epoch = ledger_->epoch();
+  p.nom_made = ledger_->nominations_made();
+  p.margin = ledger_->nomination_margin();
+  s.rcs.resize(ids.size());
+  s.scores.resize(ids.size());
+  p.node = priorities_answer(s, last.uid, s.prep_dem, ids, names, true, &p.body);
+  s.last_assume.valid = true;   // still the request's to use, should it not take this answer
+  if (p.node == -2) return;     // the filter's placements no longer hold: nothing to prepare
+  p.uid.assign(last.uid);
+  p.slot = slot;
+  p.used = idc.used[slot];
+  p.dem_hash = s.last_assume.dem_hash;
+  p.opt_seen = s.opt_seen;
+  p.valid = true;
+  prio_prepared.fetch_add(1, std::memory_order_relaxed);
+}
+
+bool Frontend::memo_ahead_step(VerbScratch& s) {
+  while (s.ahead_at < s.n_classes) {
+    const VerbScratch::Class& c = s.classes[s.ahead_at++];
+    if (c.opt_seen != s.opt_seen) continue;   // evaluated under a policy since replaced
+    IoTimer it{kFeMemoAhead};
+    int32_t rc, score;   // dropped: the call is made for this thread's plan memo
+    t_io_quiet = true;   // (timed whole, here: the ledger's kinds count what the verbs pay)
+    ledger_->assume_many(&s.ahead_node, 1, c.dem, s.opt, &rc, &score);
+    t_io_quiet = false;
+    memo_ahead.fetch_add(1, std::memory_order_relaxed);
+    if (s.ahead_at == s.n_classes) s.ahead_node = -1;
+    return true;
+  }
+  s.ahead_node = -1;
+  return false;
+}
+
+void Frontend::nominate_for_priorities(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem) {
+  if (s.defer && defer_nominate_ok(s) && s.last.valid && uid.data() == s.last.uid.data()) {
+    s.defer_nominate = true;
+    s.defer_node = node;
+    s.defer_dem = dem;
+    ledger_->deferred_nomination_begin();   // other workers' filters wait for it
+  } else {
+    IoTimer it{kFeVerbNominate};
+    ledger_->nominate(node, uid, dem, s.opt);
+    s.node_changed(node);
+  }
+  s.nom_dropped = false;
 }
 
 bool Frontend::handle_native(Worker* w, Conn* c, std::string_view method, std::string_view path,
@@ -1925,6 +2073,9 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   // a list's names are read through its token offsets into this request's text (no per-request
   // copy of 2 x N views); only a list in another shape fills nv / nraw
   const std::vector<std::pair<uint32_t, uint32_t>>* toks = nullptr;
+  // a prepared priorities answer is about one cached list as it stood (its stamp, its ids)
+  const uint64_t used_before = slot >= 0 ? idc.used[slot] : 0;
+  const bool ids_current = slot >= 0 && idc.epoch[slot] == epoch;
   if (slot >= 0) {
     // the same list text as before: its tokens sit at the same offsets (escape-free lists
     // only are cached); names and ids come from the cache
@@ -2089,6 +2240,7 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
         la.ids.assign(ids.begin(), ids.end());
         la.rcs.assign(rcs.begin(), rcs.end());
         la.scores.assign(scores.begin(), scores.end());
+        if (s.ahead) s.remember_class(dem, la.dem_hash);
       }
     }
     // decisive: the node priorities would rank first is the only one answered (and nominated)
@@ -2116,6 +2268,7 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
       } else {
         IoTimer it{kFeVerbNominate};
         ledger_->nominate(ids[nom], uid, dem, o);
+        s.node_changed(ids[nom]);
       }
       s.nom_dropped = false;
     }
@@ -2181,23 +2334,73 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
       }
     }
     r += "},\"Error\":\"\"}";
-    if (any_failed && pick < 0 && slot >= 0 && idc.valid[slot] && idc.epoch[slot] == epoch) {
-      size_t n_ok = 0;
-      for (const int32_t rc : rcs) n_ok += rc == kOk;
+    s.prep.valid = false;   // a prepared answer belongs to the latest filter
+    if (pick < 0 && slot >= 0 && idc.valid[slot] && idc.epoch[slot] == epoch) {
+      size_t n_ok = rcs.size();
+      if (any_failed) {
+        n_ok = 0;
+        for (const int32_t rc : rcs) n_ok += rc == kOk;
+      }
       if (n_ok > 1) {   // one node: kube-scheduler skips priorities
-        if (s.defer) s.defer_list = slot;
-        else idc.remember_subset(slot, rcs);
+        if (any_failed) {
+          if (s.defer) s.defer_list = slot;
+          else idc.remember_subset(slot, rcs);
+        }
+        // the priorities call that follows is answered behind this answer (run_deferred), over
+        // this list or its fitting subset
+        if (s.prepare && !decisive && s.last_assume.valid && last.valid && uid.data() == last.uid.data()) {
+          s.prep_want = true;
+          s.prep_slot = any_failed ? -1 : slot;
+          s.prep_dem = dem;
+        }
       }
     }
     return true;
   }
+  NameToks names;
+  names.text = raw_names;
+  names.toks = toks;
+  names.nraw = &nraw;
+  // the answer prepared behind this pod's filter answer, if all it was made of still reads the same
+  io_end(kFeVerbCache, io0);
+  if (s.prep.valid) {
+    VerbScratch::Prepared& p = s.prep;
+    p.valid = false;   // one use
+    const uint64_t a0 = io_t0();   // what is left of the placements on the path: this comparison
+    if (slot == p.slot && used_before == p.used && ids_current && p.opt_seen == s.opt_seen && uid == p.uid &&
+        p.dem_hash == dem.hash() && p.epoch == ledger_->epoch() && p.nom_made == ledger_->nominations_made() &&
+        p.margin == ledger_->nomination_margin()) {
+      s.last_assume.valid = false;   // the placements it was made from: used
+      r.swap(p.body);
+      io_end(kFeVerbAssume, a0);
+      if (p.node >= 0) nominate_for_priorities(s, p.node, uid, dem);
+      prio_prepared_used.fetch_add(1, std::memory_order_relaxed);
+      return true;
+    }
+    prio_prepared_stale.fetch_add(1, std::memory_order_relaxed);
+  }
   scores.resize(ids.size());
   rcs.resize(ids.size());
-  io_end(kFeVerbCache, io0);
+  const int32_t node = priorities_answer(s, uid, dem, ids, names, false, &r);
+  if (node >= 0) nominate_for_priorities(s, node, uid, dem);
+  return true;
+}
+
+int32_t Frontend::priorities_answer(VerbScratch& s, std::string_view uid, const Demand& dem,
+                                    const std::vector<int32_t>& ids, const NameToks& names, bool reuse_only,
+                                    std::string* out) {
+  std::vector<int32_t>& rcs = s.rcs;
+  std::vector<int32_t>& scores = s.scores;
+  const Options& o = s.opt;
+  const bool normalize = s.normalize, nominate = s.nominate;
+  std::string& r = *out;
   {
-    IoTimer it{kFeVerbAssume};
-    if (!reuse_assume(s, uid, dem, ids, &rcs, &scores))
+    const uint64_t a0 = reuse_only ? 0 : io_t0();   // (a prepared answer is timed whole, off the path)
+    if (!reuse_assume(s, uid, dem, ids, &rcs, &scores)) {
+      if (reuse_only) return -2;
       ledger_->assume_many(ids.data(), static_cast<int>(ids.size()), dem, o, rcs.data(), scores.data());
+    }
+    io_end(kFeVerbAssume, a0);
   }
   int64_t best = -1;
   int n_best = 0;
@@ -2231,22 +2434,8 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
     n_best = 1;
   }
   const bool lead = n_best == 1 && (second < 0 || scores[best] - second >= margin);
-  bool nominated = false;
-  if (nominate && lead && !uid.empty() && dem.n > 0) {
-    if (wants_devices(dem)) {
-      if (s.defer && defer_nominate_ok(s) && last.valid && uid.data() == last.uid.data()) {
-        s.defer_nominate = true;
-        s.defer_node = ids[best];
-        s.defer_dem = dem;
-        ledger_->deferred_nomination_begin();   // other workers' filters wait for it
-      } else {
-        IoTimer it{kFeVerbNominate};
-        ledger_->nominate(ids[best], uid, dem, o);
-      }
-      s.nom_dropped = false;
-      nominated = true;
-    }
-  }
+  // (the nomination itself is the caller's to make: nominate_for_priorities, with the node returned)
+  const bool nominated = nominate && lead && !uid.empty() && dem.n > 0 && wants_devices(dem);
   // The nomination is the pod's placement from this answer on: every later filter sees its
   // devices held. kube-scheduler adds its own score plugins (LeastAllocated, BalancedAllocation,
   // PodTopologySpread: about 800 points between nodes at most) to 10 x the extender's score, so a
@@ -2284,13 +2473,13 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   // worst case (no per-append capacity checks: 420 nodes are 2,000 small writes)
   constexpr std::string_view kHost = "{\"Host\":", kScore = ",\"Score\":";
   size_t cap = 2;
-  for (size_t i = 0; i < ids.size(); ++i) cap += raw_at(i).size() + kHost.size() + kScore.size() + 14;
+  for (size_t i = 0; i < ids.size(); ++i) cap += names.raw_at(i).size() + kHost.size() + kScore.size() + 14;
   r.resize(cap);
   char* w = r.data();
   *w++ = '[';
   for (size_t i = 0; i < ids.size(); ++i) {
     if (i) *w++ = ',';
-    const std::string_view tok = raw_at(i);
+    const std::string_view tok = names.raw_at(i);
     std::memcpy(w, kHost.data(), kHost.size());
     w += kHost.size();
     std::memcpy(w, tok.data(), tok.size());
@@ -2302,7 +2491,7 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   }
   *w++ = ']';
   r.resize(static_cast<size_t>(w - r.data()));
-  return true;
+  return nominated ? ids[best] : -1;
 }
 
 }  // namespace nanogpu
