@@ -29,6 +29,8 @@ format, joined with what it granted:
     nanogpu_selftest_valu_checked{device}                            groups the last run checked on every CU
   per device, when the deep self-test also ran the scalar part (--selftest-scalar; absent otherwise)
     nanogpu_selftest_scalar_checked{device}                          groups the last run checked on every CU
+  per device, when the deep self-test also ran the memory part (--selftest-mem; absent otherwise)
+    nanogpu_selftest_mem_checked{device}                             groups the last run checked on every CU
   per device, only with --selftest-fence (agent/node.py: a failing CU's mask unit is fenced, not the GPU)
     nanogpu_selftest_fenced_cus{device}                              CUs in fenced units
     nanogpu_selftest_fenced_units_in_use{device}                     fenced units a grant from before still holds

@@ -140,7 +140,7 @@ class NodeAgent:
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
                  selftest_period_s: float = 0.0, selftest_paths=None, selftest_fence: int = 0,
-                 selftest_fence_reset: bool = False, selftest_valu=None, selftest_scalar=None):
+                 selftest_fence_reset: bool = False, selftest_valu=None, selftest_scalar=None, selftest_mem=None):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -157,7 +157,7 @@ class NodeAgent:
         from ..probe.selftest import Selection
 
         # what every deep sweep also runs of each optional part ("all", "a,b" or names); any of them makes the sweep deep
-        self.selftest_parts = Selection.parse(paths=selftest_paths, valu=selftest_valu, scalar=selftest_scalar)
+        self.selftest_parts = Selection.parse(paths=selftest_paths, valu=selftest_valu, scalar=selftest_scalar, mem=selftest_mem)
         if any(vars(self.selftest_parts).values()):
             self.selftest_deep = True
         self._no_paths_logged = False
@@ -647,7 +647,7 @@ def build_parser():
 
     for part in PARTS:
         ap.add_argument(f"--selftest-{part.key}", action=_Names, const=part, default=[], metavar="all|LIST",
-                        help=part.agent_help)
+                        help=part.agent_help if part.listed else argparse.SUPPRESS)
 
     class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
         def __call__(self, parser, ns, values, option_string=None):

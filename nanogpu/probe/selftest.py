@@ -18,7 +18,9 @@ exports; `deep_selftest`, the report, the fence helpers and `main` loop over tha
 (`selftest_paths.py`) takes `cu_sweep`'s place in the sweep's own launch and adds an exact chain of each
 selected matrix path to every visit. `cu_sweep_valu` (`selftest_valu.py`: vector ALU, transcendentals, VGPR
 file) and `cu_sweep_scalar` (`selftest_scalar.py`: scalar ALU, vector / scalar boundary, scalar loads, SGPR
-file) are further launches on the same mask after each sweep launch, with records of their own.
+file) are further launches on the same mask after each sweep launch, with records of their own, and so is
+`cu_sweep_mem` (`selftest_mem.py`: the CU's memory pipeline: global and buffer loads and stores, the L1, LDS forms,
+LDS-DMA, atomics), the last one.
 
 What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
 and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache, and of
@@ -30,7 +32,7 @@ runs `deep_selftest` once per candidate unit, masked to it, and says which units
 which failing CUs no such unit explains. The agent fences those units (`--selftest-fence`)
 instead of failing the device when `fenceable` allows it.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--scalar all|LIST] [--json]`
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--scalar all|LIST] [--mem all|LIST] [--json]`
 prints one report;
 with `--fence N` it also prints the units (at most N) an agent would fence, and changes nothing.
 """
@@ -40,12 +42,12 @@ import logging
 import time
 from dataclasses import asdict, dataclass, field, make_dataclass
 
-from . import selftest_common, selftest_paths, selftest_scalar, selftest_valu
+from . import selftest_common, selftest_mem, selftest_paths, selftest_scalar, selftest_valu
 from .selftest_common import HI_MUL, M32, Part, by_cu, coverage, cu_key, mix32, or_all, simds_seen_min
 
 log = logging.getLogger(__name__)
 
-PARTS: tuple[Part, ...] = (selftest_paths.PART, selftest_valu.PART, selftest_scalar.PART)   # in the order they launch
+PARTS: tuple[Part, ...] = (selftest_paths.PART, selftest_valu.PART, selftest_scalar.PART, selftest_mem.PART)   # in the order they launch
 FAIL_LDS = 1 << 4            # fail bits 0..3: the MFMA check of wave 0..3
 HBM_HEADROOM = 2 << 30       # left free by the "all free HBM" check
 MAX_LAUNCHES = 3
@@ -124,6 +126,7 @@ class DeepReport:
     # {"checked": [names], "failed": {kind: [[xcc, cu_key], ...]}, "cus": its fold's, [s]reg_slots, "ms"}; None: not run
     valu: dict | None = field(default=None, repr=False)
     scalar: dict | None = field(default=None, repr=False)
+    mem: dict | None = field(default=None, repr=False)
 
     def to_dict(self) -> dict:
         """What /metrics and --json show: every field but `cu_keys`, as before that field existed;
@@ -220,7 +223,7 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
     whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory, on a stream
     with the same mask when one is given (a probe that cannot gets a note and no HBM check).
     `select` holds one keyword per part of `PARTS` to run (`Selection.parse`: `paths=`, `valu=`,
-    `scalar=`, each None, "all", "a,b" or a list of names). A part without a launch of its own
+    `scalar=`, `mem=`, each None, "all", "a,b" or a list of names). A part without a launch of its own
     (the matrix paths) makes the sweep launches its binding instead of `cu_sweep`: still one visit
     per CU. Every other selected part adds, after each sweep launch of the coverage loop, a launch
     of its binding on the same mask, in the order of `PARTS`. A part this probe has no binding for
@@ -385,7 +388,7 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--hbm-mib", type=int, default=1024,
                     help="HBM to pattern-check in MiB (default 1024; 0: all free memory less 2 GiB)")
     for part in PARTS:
-        ap.add_argument(f"--{part.key}", default="", metavar="all|LIST", help=part.help)
+        ap.add_argument(f"--{part.key}", default="", metavar="all|LIST", help=part.help if part.listed else argparse.SUPPRESS)
     ap.add_argument("--fence", type=int, default=0, metavar="N",
                     help="after a failed sweep, print the CU-mask units (at most N) and CUs an agent started with "
                          "--selftest-fence N would fence; changes nothing on the device or the node")

@@ -1,6 +1,6 @@
 """What the parts of the deep self-test and its orchestration share: the hashes and checksums of the
 host twins, the folding of per-visit records by CU, the parsing of name lists, and `Part`, the
-description each optional part (`selftest_paths`, `selftest_valu`, `selftest_scalar`) gives of
+description each optional part (`selftest_paths`, `selftest_valu`, `selftest_scalar`, `selftest_mem`) gives of
 itself to `selftest.py`, the agent and /metrics. This module imports none of them."""
 from __future__ import annotations
 
@@ -120,6 +120,7 @@ class Part:
     note_unreached: str = ""    # a format over n, the CUs its launches did not reach
     failed_metric: tuple[str, str, str] | None = None   # (family, label, help) of a gauge of failed CUs per name
     none_in_dict: bool = False  # to_dict() shows the part, as None, when it did not run
+    listed: bool = True         # --help shows its flags; False: they parse all the same
 
     def parse(self, spec) -> list[str]:
         """`parse_names` over this part's names."""

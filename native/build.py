@@ -6,7 +6,7 @@ Outputs (git-ignored, but shipped to the GPU box by gpurun):
   native/bin/nanogpu-topo   standalone topology CLI (node agent without Python)
 
 Usage: python native/build.py [--force] [--no-hip] [--sanitize address|thread|undefined]
-                              [--stress plain|asan|tsan] [--selftest-host plain|asan|paths-plain|paths-asan|valu-plain|valu-asan|scalar-plain|scalar-asan]
+                              [--stress plain|asan|tsan] [--selftest-host plain|asan|paths-plain|paths-asan|valu-plain|valu-asan|scalar-plain|scalar-asan|mem-plain|mem-asan]
 """
 from __future__ import annotations
 
@@ -144,13 +144,15 @@ SELFTEST_HOST_TARGETS = {   # target -> (program's stem, its main, the headers i
              ["selftest_host.h", "selftest_paths_host.h", "selftest_valu_host.h"]),
     "scalar": ("nanogpu-selftest-scalar-host", "selftest_scalar_host_main.cpp",
                ["selftest_host.h", "selftest_paths_host.h", "selftest_scalar_host.h"]),
+    "mem": ("nanogpu-selftest-mem-host", "selftest_mem_host_main.cpp",
+            ["selftest_host.h", "selftest_paths_host.h", "selftest_mem_host.h"]),
 }
 
 
 def build_selftest_host(kind: str = "plain", force: bool = False, target: str = "host") -> Path:
     """Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h, or
     with target "paths" nanogpu/selftest_paths_host.h, with "valu" nanogpu/selftest_valu_host.h, with "scalar"
-    nanogpu/selftest_scalar_host.h, which the
+    nanogpu/selftest_scalar_host.h, with "mem" nanogpu/selftest_mem_host.h, which the
     probe's kernels share),
     optionally under ASan+UBSan. No GPU code involved."""
     stem, main_cpp, headers = SELFTEST_HOST_TARGETS[target]
@@ -197,9 +199,9 @@ def main() -> None:
     ap.add_argument("--sanitize", choices=["address", "thread", "undefined"])
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
     ap.add_argument("--selftest-host", choices=["plain", "asan", "paths-plain", "paths-asan", "valu-plain", "valu-asan", "scalar-plain",
-                                               "scalar-asan"],
+                                               "scalar-asan", "mem-plain", "mem-asan"],
                     help="build the stand-alone check of the deep self-test's host arithmetic "
-                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups')")
+                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups')")
     a = ap.parse_args()
     if a.stress:
         print(build_stress(a.stress, force=a.force))
