@@ -1,7 +1,7 @@
 """Deep GPU self-test: every CU's MFMA pipes and LDS, and free HBM with an address pattern.
 
 The basic self-test (agent.node.gpu_selftest) runs one wave on one CU and copies 16 MiB. This
-one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe.hip):
+one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe_sweep.inc, probe_hbm.inc):
 
 * `cu_sweep` launches rounds x CUs workgroups that each hold a CU's whole LDS (so at most one
   is resident per CU and the dispatcher spreads them), run an exact bf16 MFMA chain on all 4

@@ -1,6 +1,6 @@
 """Memory part of the deep self-test: the Python twin of native/include/nanogpu/selftest_mem_host.h.
 
-`cu_sweep_mem` (native/hip/probe.hip) makes all four waves of every CU run the memory pipeline: global
+`cu_sweep_mem` (native/hip/probe_mem.inc) makes all four waves of every CU run the memory pipeline: global
 loads of every width and extension (`gload`), the whole 32 KiB table twice through the CU's L1 (`l1`),
 global stores of every width over a background (`gstore`), raw buffer loads and stores with lanes in
 and out of range (`buffer`), the LDS instruction forms (`lds`), the transposed LDS read (`ldstr`),

@@ -1,6 +1,6 @@
 """Matrix-path part of the deep self-test: the Python twin of native/include/nanogpu/selftest_paths_host.h.
 
-`cu_sweep_paths` (native/hip/probe.hip) is `cu_sweep` with, in every visit, an exact chain of 8
+`cu_sweep_paths` (native/hip/probe_sweep.inc) is `cu_sweep` with, in every visit, an exact chain of 8
 instructions of each selected matrix path (`PATHS`) on all 4 waves, every accumulator compared bit
 for bit with a host tile. The operand data is generated as codes and decoded on the host; the
 decoders, generators and expected tiles below are the twin of the header, which states the

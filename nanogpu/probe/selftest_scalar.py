@@ -1,6 +1,6 @@
 """Scalar part of the deep self-test: the Python twin of native/include/nanogpu/selftest_scalar_host.h.
 
-`cu_sweep_scalar` (native/hip/probe.hip) makes all four waves of every CU run exact chains of
+`cu_sweep_scalar` (native/hip/probe_scalar.inc) makes all four waves of every CU run exact chains of
 scalar-ALU instructions (`EXACT_GROUPS`: add, mul, shift, logic, bits, cmp and the vector / scalar
 boundary vcc), scalar loads of a read-only table (`smem`) and a pattern test of the wave's scalar
 registers (`sregs`). This module computes what the exact groups must give, in plain Python integers:

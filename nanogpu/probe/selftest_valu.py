@@ -1,6 +1,6 @@
 """Vector-ALU part of the deep self-test: the Python twin of native/include/nanogpu/selftest_valu_host.h.
 
-`cu_sweep_valu` (native/hip/probe.hip) makes all four waves of every CU run exact chains of
+`cu_sweep_valu` (native/hip/probe_valu.inc) makes all four waves of every CU run exact chains of
 vector-ALU instructions (`GROUPS[:NUM_EXACT]`), the transcendental instructions (`approx`) and a
 pattern test of the SIMD's vector register file (`regs`). This module computes what the exact
 groups must give, in Python integers and `fractions.Fraction` (every IEEE step is the exact

@@ -6,7 +6,8 @@ Outputs (git-ignored, but shipped to the GPU box by gpurun):
   native/bin/nanogpu-topo   standalone topology CLI (node agent without Python)
 
 Usage: python native/build.py [--force] [--no-hip] [--sanitize address|thread|undefined]
-                              [--stress plain|asan|tsan] [--selftest-host plain|asan|paths-plain|paths-asan|valu-plain|valu-asan|scalar-plain|scalar-asan|mem-plain|mem-asan]
+                              [--stress plain|asan|tsan] [--selftest-host plain|asan|<target>-plain|<target>-asan]
+                              (one <target> per entry of SELFTEST_HOST_TARGETS besides "host")
 """
 from __future__ import annotations
 
@@ -147,13 +148,14 @@ SELFTEST_HOST_TARGETS = {   # target -> (program's stem, its main, the headers i
     "mem": ("nanogpu-selftest-mem-host", "selftest_mem_host_main.cpp",
             ["selftest_host.h", "selftest_paths_host.h", "selftest_mem_host.h"]),
 }
+# --selftest-host's values: "plain" and "asan" for target "host", "<target>-plain" and "<target>-asan" for the others
+SELFTEST_HOST_CHOICES = [kind if target == "host" else f"{target}-{kind}"
+                         for target in SELFTEST_HOST_TARGETS for kind in ("plain", "asan")]
 
 
 def build_selftest_host(kind: str = "plain", force: bool = False, target: str = "host") -> Path:
-    """Stand-alone check of the deep self-test's host arithmetic (nanogpu/selftest_host.h, or
-    with target "paths" nanogpu/selftest_paths_host.h, with "valu" nanogpu/selftest_valu_host.h, with "scalar"
-    nanogpu/selftest_scalar_host.h, with "mem" nanogpu/selftest_mem_host.h, which the
-    probe's kernels share),
+    """Stand-alone check of the deep self-test's host arithmetic, one program per target of
+    SELFTEST_HOST_TARGETS (the headers it names, which the probe's kernels share),
     optionally under ASan+UBSan. No GPU code involved."""
     stem, main_cpp, headers = SELFTEST_HOST_TARGETS[target]
     out = NATIVE / "bin" / f"{stem}-{kind}"
@@ -173,8 +175,8 @@ def build_probe(force: bool = False) -> Path | None:
     if not Path(hipcc).exists():
         return None
     out = PKG / f"_probe{EXT}"
-    srcs = [NATIVE / "hip" / "probe.hip"]
-    deps = srcs + _headers() + [Path(__file__)]
+    srcs = [NATIVE / "hip" / "probe.hip"]   # one translation unit: it includes the other files under hip/
+    deps = sorted(p for p in (NATIVE / "hip").rglob("*") if p.is_file()) + _headers() + [Path(__file__)]
     if not force and _fresh(out, deps, [ARCH]):
         return out
     BUILD.mkdir(parents=True, exist_ok=True)
@@ -198,8 +200,7 @@ def main() -> None:
     ap.add_argument("--no-hip", action="store_true")
     ap.add_argument("--sanitize", choices=["address", "thread", "undefined"])
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
-    ap.add_argument("--selftest-host", choices=["plain", "asan", "paths-plain", "paths-asan", "valu-plain", "valu-asan", "scalar-plain",
-                                               "scalar-asan", "mem-plain", "mem-asan"],
+    ap.add_argument("--selftest-host", choices=SELFTEST_HOST_CHOICES,
                     help="build the stand-alone check of the deep self-test's host arithmetic "
                          "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups')")
     a = ap.parse_args()

@@ -1,4 +1,4 @@
-// Host/device-shared arithmetic of the deep self-test (native/hip/probe.hip: cu_sweep,
+// Host/device-shared arithmetic of the deep self-test (native/hip/probe_sweep.inc: cu_sweep; probe_hbm.inc:
 // hbm_fill, hbm_verify). Plain C++ with no HIP dependency, so the host side can be built
 // and run under sanitizers on its own (native/tests/selftest_host_main.cpp). The Python
 // twin of the pattern is nanogpu/probe/selftest.py.

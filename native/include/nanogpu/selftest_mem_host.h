@@ -1,4 +1,4 @@
-// Host/device-shared definitions of the deep self-test's memory part (native/hip/probe.hip:
+// Host/device-shared definitions of the deep self-test's memory part (native/hip/probe_mem.inc:
 // cu_mem_kernel, mem_lanes_kernel). Plain C++ with no HIP dependency: the stand-alone program
 // native/tests/selftest_mem_host_main.cpp builds it on its own, also under ASan + UBSan. The Python
 // twin, in plain integers, is nanogpu/probe/selftest_mem.py.

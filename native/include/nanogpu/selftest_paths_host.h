@@ -1,4 +1,4 @@
-// Host/device-shared arithmetic of the deep self-test's matrix paths (native/hip/probe.hip:
+// Host/device-shared arithmetic of the deep self-test's matrix paths (native/hip/probe_sweep.inc:
 // matrix_tile, cu_sweep_paths). A path is one MFMA instruction plus its operand formats.
 // Plain C++ with no HIP dependency: native/tests/selftest_paths_host_main.cpp builds and runs
 // the host side on its own, under sanitizers too. The Python twin is nanogpu/probe/selftest.py.

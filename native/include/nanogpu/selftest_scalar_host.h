@@ -1,4 +1,4 @@
-// Host/device-shared arithmetic of the deep self-test's scalar part (native/hip/probe.hip:
+// Host/device-shared arithmetic of the deep self-test's scalar part (native/hip/probe_scalar.inc:
 // cu_scalar_kernel, scalar_words_kernel). Plain C++ with no HIP dependency: the stand-alone program
 // native/tests/selftest_scalar_host_main.cpp builds it on its own, also under ASan + UBSan. The
 // Python twin, in plain integers, is nanogpu/probe/selftest_scalar.py.

@@ -1,4 +1,4 @@
-// Host/device-shared arithmetic of the deep self-test's vector-ALU part (native/hip/probe.hip:
+// Host/device-shared arithmetic of the deep self-test's vector-ALU part (native/hip/probe_valu.inc:
 // cu_valu_kernel, valu_lanes_kernel). Plain C++ with no HIP dependency: the stand-alone program
 // native/tests/selftest_valu_host_main.cpp builds it on its own, also under ASan + UBSan. The
 // Python twin, in integers and fractions, is nanogpu/probe/selftest_valu.py.
