@@ -199,8 +199,19 @@ class Frontend {
   bool spin_recv_conn(Worker* w, uint64_t cid);
   void process(Worker* w, Conn* c);
   // the verb's whole HTTP answer appended to *out (false: not a native verb, nothing written)
-  bool handle_native(Worker* w, Conn* c, std::string_view method, std::string_view path, std::string_view body,
+  bool handle_native(Worker* w, std::string_view method, std::string_view path, std::string_view body,
                      std::string* out);
+  // filter_verb's stages, in the order it runs them (false: the request needs the Python path)
+  struct VerbCall;   // one request as the stages hand it on (frontend.cpp)
+  static bool frame(std::string_view body, VerbScratch& s, VerbCall* c);
+  bool read_pod(VerbScratch& s, VerbCall* c);
+  bool resolve_list(VerbScratch& s, VerbCall* c);
+  void refresh_options(VerbScratch& s);
+  void drop_and_cache(VerbScratch& s, const VerbCall& c, bool prioritize);
+  void filter_answer(VerbScratch& s, const VerbCall& c, std::string* out);
+  static bool write_filter_reply(VerbScratch& s, const VerbCall& c, int64_t pick, std::string* out);
+  static void arrange_deferred(VerbScratch& s, const VerbCall& c, bool any_failed, bool decisive);
+  void priorities(VerbScratch& s, const VerbCall& c, std::string* out);
   void defer(Worker* w, Conn* c, std::string method, std::string path, std::string query, std::string body);
   void flush(Worker* w, Conn* c, int io_kind = kFeSendOther);
   void close_conn(Worker* w, Conn* c);
@@ -209,11 +220,6 @@ class Frontend {
   void prepare_bind(std::string_view body, PyRequest* r, VerbScratch& s);
   void cache_pod(VerbScratch& s, std::string_view uid, const CachedPod& cached, std::string_view raw, const Demand& dem);
   void run_deferred(VerbScratch& s);   // a worker verb's work left for after its answer went out
-  // a nomination may wait until after the answer with one worker thread (this worker reads
-  // nothing in between). kube-scheduler's next filter may reach another worker process: the
-  // ledger counts the deferred nominations, and that filter waits until they are made
-  // (Ledger::wait_deferred_nominations), so it never sees the ledger without this pod's devices
-  bool defer_nominate_ok(const VerbScratch& s) const;
   // priorities right behind its pod's filter, nothing changed since: the filter's placements
   bool reuse_assume(VerbScratch& s, std::string_view uid, const Demand& dem, const std::vector<int32_t>& ids,
                     std::vector<int32_t>* rcs, std::vector<int32_t>* scores);
@@ -224,8 +230,13 @@ class Frontend {
   struct NameToks;
   int32_t priorities_answer(VerbScratch& s, std::string_view uid, const Demand& dem, const std::vector<int32_t>& ids,
                             const NameToks& names, bool reuse_only, std::string* out);
-  // the nomination priorities_answer asked for: after the answer on a worker, else now
-  void nominate_for_priorities(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem);
+  // the nomination a verb's answer decided on (the filter's pick or only fitting node, the node
+  // priorities_answer returned), made now or, on a worker, after the answer. It may wait until
+  // then with one worker thread (this worker reads nothing in between). kube-scheduler's next
+  // filter may reach another worker process: the ledger counts the deferred nominations, and
+  // that filter waits until they are made (Ledger::wait_deferred_nominations), so it never sees
+  // the ledger without this pod's devices
+  void nominate_or_defer(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem);
   // run_deferred: the answer of the priorities request that follows the filter just answered
   void prepare_priorities(VerbScratch& s);
   // one remembered demand class evaluated on the node a nomination / reservation just changed

@@ -522,9 +522,7 @@ struct PhaseTimer {
   uint64_t t0 = fast_ns();
   ~PhaseTimer() { atomic_max(m, fast_ns() - t0); }
 };
-}  // namespace
 
-namespace {
 // priorities follows its cycle's filter with the same Pod text on the same connection, so on
 // the same worker: the pod a worker parsed last is reused when the text is identical (demand,
 // identity, containers); only the learned-owner flag is read again
@@ -632,7 +630,7 @@ struct Frontend::VerbScratch {
   // next request of the cycle no longer waits on them. Off for callers off the workers (tests,
   // time_verb), which get the work done in the verb.
   bool defer = false;
-  bool defer_cache = false;   // the pod-cache put too: only with one worker thread (see filter_verb)
+  bool defer_cache = false;   // the pod-cache put and the nomination: only with one worker thread (drop_and_cache)
   bool defer_put = false;
   bool defer_nominate = false;
   int defer_list = -1;   // the filter's node-list slot whose fitting subset priorities will send
@@ -693,14 +691,36 @@ struct Frontend::VerbScratch {
   }
 };
 
-// a list's names as its request tokens: offsets into the list's text, or views of their own
+// a list's names as its request tokens: offsets into the list's text (no per-request copy of
+// 2 x N views), or, for a list in another shape, views of their own (tokens and names)
 struct Frontend::NameToks {
   std::string_view text;
   const std::vector<std::pair<uint32_t, uint32_t>>* toks = nullptr;
   const std::vector<std::string_view>* nraw = nullptr;
+  const std::vector<std::string_view>* nv = nullptr;
+  size_t size() const { return toks ? toks->size() : nv->size(); }
   std::string_view raw_at(size_t i) const {
     return toks ? text.substr((*toks)[i].first, (*toks)[i].second) : (*nraw)[i];
   }
+  std::string_view name_at(size_t i) const {
+    return toks ? text.substr((*toks)[i].first + 1, (*toks)[i].second - 2) : (*nv)[i];
+  }
+};
+
+// One filter / priorities request as filter_verb's stages hand it on
+struct Frontend::VerbCall {
+  std::string_view pod_text, raw_names;   // (frame)
+  bool reused = false;   // the pod text is the last pod's: taken from LastPod, not parsed
+  int32_t pod = -1;      // the pod parsed for this request: its root in VerbScratch::d
+  int found = -2;        // the list's cache slot as frame found it; -1: none, tokens scanned into s.ntok; -2: not looked up
+  Demand dem;             // (read_pod)
+  std::string_view uid;
+  uint64_t node_epoch = 0;   // (resolve_list) Ledger::node_epoch the ids are current at
+  int slot = -1;             // the list's IdCache slot: its ids are idc.ids[slot]
+  NameToks names;
+  // a prepared priorities answer is about one cached list as it stood (its stamp, its ids)
+  uint64_t used_before = 0;
+  bool ids_current = false;
 };
 
 // ------------------------------------------------------------------------------ plumbing
@@ -1589,7 +1609,7 @@ void Frontend::process(Worker* w, Conn* c) {
       query = target.substr(qm + 1);
     }
     const bool prio = path == "/scheduler/priorities";   // `path` views c->in, erased below
-    if (handle_native(w, c, method, path, body, &c->out)) {   // the answer lands in c->out
+    if (handle_native(w, method, path, body, &c->out)) {   // the answer lands in c->out
       const uint64_t t_in = c->t_in_ns;
       c->in.erase(0, consumed);
       if (!c->in.empty()) c->t_in_ns = fast_ns();   // a pipelined request behind it: its own clock
@@ -1708,14 +1728,11 @@ void Frontend::cache_pod(VerbScratch& s, std::string_view uid, const CachedPod& 
                          const Demand& dem) {
   if (ledger_->attached() > 1) {
     // other worker processes share the ledger: the bind may reach one of them
-    std::string& blob = s.blob;
-    pack_pod(cached, dem, &blob);
-    if (ledger_->put_pod_info(uid, blob)) pods_published.fetch_add(1, std::memory_order_relaxed);
+    pack_pod(cached, dem, &s.blob);
+    if (ledger_->put_pod_info(uid, s.blob)) pods_published.fetch_add(1, std::memory_order_relaxed);
   }
   put_pod(uid, cached, raw, dem);
 }
-
-bool Frontend::defer_nominate_ok(const VerbScratch& s) const { return s.defer_cache; }
 
 bool Frontend::reuse_assume(VerbScratch& s, std::string_view uid, const Demand& dem, const std::vector<int32_t>& ids,
                             std::vector<int32_t>* rcs, std::vector<int32_t>* scores) {
@@ -1782,9 +1799,7 @@ void Frontend::prepare_priorities(VerbScratch& s) {
   const LastPod& last = s.last;
   if (!last.valid || !idc.valid[slot] || !s.last_assume.valid) return;
   const std::vector<int32_t>& ids = idc.ids[slot];
-  NameToks names;
-  names.text = idc.text[slot];
-  names.toks = &idc.tok[slot];
+  const NameToks names{idc.text[slot], &idc.tok[slot]};
   // read before the placements are: a change after this point shows in the key, one before it
   // in the placements' own epoch check
   p.epoch = ledger_->epoch();
@@ -1821,8 +1836,8 @@ bool Frontend::memo_ahead_step(VerbScratch& s) {
   return false;
 }
 
-void Frontend::nominate_for_priorities(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem) {
-  if (s.defer && defer_nominate_ok(s) && s.last.valid && uid.data() == s.last.uid.data()) {
+void Frontend::nominate_or_defer(VerbScratch& s, int32_t node, std::string_view uid, const Demand& dem) {
+  if (s.defer_cache && s.last.valid && uid.data() == s.last.uid.data()) {
     s.defer_nominate = true;
     s.defer_node = node;
     s.defer_dem = dem;
@@ -1835,9 +1850,8 @@ void Frontend::nominate_for_priorities(VerbScratch& s, int32_t node, std::string
   s.nom_dropped = false;
 }
 
-bool Frontend::handle_native(Worker* w, Conn* c, std::string_view method, std::string_view path,
-                             std::string_view body, std::string* out) {
-  (void)c;
+bool Frontend::handle_native(Worker* w, std::string_view method, std::string_view path, std::string_view body,
+                             std::string* out) {
   if (method != "POST" || !serving()) return false;
   const bool prio = path == "/scheduler/priorities";
   if (!prio && path != "/scheduler/filter") return false;
@@ -1846,14 +1860,7 @@ bool Frontend::handle_native(Worker* w, Conn* c, std::string_view method, std::s
   IoTimer it{kFeVerb};
   if (!filter_verb(body, prio, &resp, w->scratch)) return false;
   (prio ? prio_stats : filter_stats).observe(fast_ns() - t0);
-  constexpr std::string_view kHead = "HTTP/1.1 200 OK\r\nContent-Type: application/json; charset=utf-8\r\nContent-Length: ";
-  char len[24];
-  const char* e = std::to_chars(len, len + sizeof len, resp.size()).ptr;
-  out->reserve(out->size() + kHead.size() + 24 + resp.size());
-  *out += kHead;
-  out->append(len, static_cast<size_t>(e - len));
-  *out += "\r\n\r\n";
-  *out += resp;
+  append_http(out, 200, "application/json; charset=utf-8", resp);
   return true;
 }
 
@@ -1862,18 +1869,36 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   return filter_verb(body, prioritize, out, s);
 }
 
+// Both verbs, as their stages in order. A stage that answers false leaves the request to the
+// Python path (and the tally span it was in unrecorded).
 bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* out, VerbScratch& s) {
+  uint64_t io0 = io_t0();
+  if (s.idc.owner != serial_) s.idc = IdCache{}, s.idc.owner = serial_;
+  if (body.empty()) return false;
+  VerbCall c;
+  if (!frame(body, s, &c) || !read_pod(s, &c)) return false;
+  io_end(kFeVerbPod, io0);
+  io0 = io_t0();
+  if (!resolve_list(s, &c)) return false;
+  refresh_options(s);
+  io_end(kFeVerbNames, io0);
+  // a nomination another worker left for after its answer is made before this verb reads the
+  // ledger (this worker's own ran before it read this request); bounded
+  if (s.nominate && ledger_->attached() > 1) ledger_->wait_deferred_nominations(kDeferredNominationWaitNs);
+  io0 = io_t0();
+  drop_and_cache(s, c, prioritize);
+  out->reserve(64 + 128 * c.names.size());   // room for a FailedNodes entry per node
+  io_end(kFeVerbCache, io0);
+  if (prioritize) priorities(s, c, out);
+  else filter_answer(s, c, out);
+  return true;
+}
+
+// where the pod's text and the node list's are in the body; the pod parsed (s.d) unless it is the last one's
+bool Frontend::frame(std::string_view body, VerbScratch& s, VerbCall* c) {
   json::Doc& top = s.top;
   json::Doc& d = s.d;
-  std::vector<std::string_view>& nv = s.nv;
-  std::vector<std::string_view>& nraw = s.nraw;
-  std::vector<int32_t>& rcs = s.rcs;
-  std::vector<int32_t>& scores = s.scores;
-  LastPod& last = s.last;
-  IdCache& idc = s.idc;
-  uint64_t io0 = io_t0();
-  if (idc.owner != serial_) idc = IdCache{}, idc.owner = serial_;
-  if (body.empty()) return false;
+  const LastPod& last = s.last;
   // kube-scheduler's ExtenderArgs as Go's encoding/json writes them (struct field order, no
   // spaces): {"Pod":{...},"Nodes":null,"NodeNames":[...]}. In that exact layout the pod's text
   // is found by comparing it with the last pod's (priorities, and every retry, sends the same
@@ -1881,175 +1906,162 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   // pass over the body just to find where its members end. Any other layout takes the general
   // path below (a shallow parse of the top level, then the members).
   constexpr std::string_view kHead = "{\"Pod\":", kMid = ",\"Nodes\":null,\"NodeNames\":";
-  std::string_view pod_text, raw_names;
-  bool framed = false, reused = false, has_pod_text = false;
-  bool scanned = false;   // s.ntok holds raw_names' tokens (a list not in the cache)
-  int found = -2;         // the list's cache slot when the framing looked it up (-1: none)
-  int32_t pod = -1;
-  nv.clear();
-  nraw.clear();
   if (body.size() > kHead.size() + kMid.size() + 4 && body.compare(0, kHead.size(), kHead) == 0 &&
       body[kHead.size()] == '{' && body.back() == '}') {
     const std::string_view rest = body.substr(kHead.size());
-    size_t pe = 0;
-    bool same = false;
-    if (last.valid && rest.size() > last.raw.size() && std::memcmp(rest.data(), last.raw.data(), last.raw.size()) == 0) {
-      pe = last.raw.size();
-      same = true;
-    } else if (!d.parse_prefix(rest, &pe) || !d.is(d.root(), json::Type::kObj)) {
-      pe = 0;
-    }
-    if (pe) {
-      const std::string_view tail = rest.substr(pe);
-      if (tail.size() > kMid.size() + 2 && tail.compare(0, kMid.size(), kMid) == 0 && tail[kMid.size()] == '[' &&
-          tail[tail.size() - 2] == ']') {
-        raw_names = tail.substr(kMid.size(), tail.size() - kMid.size() - 1);
-        // the list must be one: a cached text, or a compact string array scanned whole
-        // (anything else, members after it included, goes the general way)
-        found = idc.find(raw_names);
-        if (found < 0) s.ntok.clear();
-        framed = found >= 0 || (scanned = scan_string_array(raw_names, &s.ntok));
-        if (framed) {
-          has_pod_text = true;
-          pod_text = rest.substr(0, pe);
-          reused = same;
-          if (!same) pod = d.root();
-        } else {
-          nv.clear();
-          nraw.clear();
-        }
+    const bool same =
+        last.valid && rest.size() > last.raw.size() && std::memcmp(rest.data(), last.raw.data(), last.raw.size()) == 0;
+    size_t pe = same ? last.raw.size() : 0;
+    if (!same && (!d.parse_prefix(rest, &pe) || !d.is(d.root(), json::Type::kObj))) pe = 0;
+    const std::string_view tail = rest.substr(pe);
+    if (pe && tail.size() > kMid.size() + 2 && tail.compare(0, kMid.size(), kMid) == 0 && tail[kMid.size()] == '[' &&
+        tail[tail.size() - 2] == ']') {
+      c->raw_names = tail.substr(kMid.size(), tail.size() - kMid.size() - 1);
+      // the list must be one: a cached text, or a compact string array scanned whole
+      // (anything else, members after it included, goes the general way)
+      c->found = s.idc.find(c->raw_names);
+      if (c->found < 0) s.ntok.clear();
+      if (c->found >= 0 || scan_string_array(c->raw_names, &s.ntok)) {
+        c->pod_text = rest.substr(0, pe);
+        c->reused = same;
+        if (!same) c->pod = d.root();
+        return true;
       }
+      c->found = -2;   // the list the general way finds may be another text
     }
   }
-  if (!framed) {
-    // The body's top level only (Pod and NodeNames stay unparsed text), then the Pod on its own
-    // (`d`); the node-name list is parsed only when this worker has not seen that exact text.
-    if (!top.parse_shallow(body, 1)) return false;
-    const int32_t root = top.root();
-    if (!top.is(root, json::Type::kObj)) return false;
-    const int32_t names = top.get(root, "NodeNames", true);
-    if (!top.is(names, json::Type::kArr)) return false;     // null / Nodes-only: Python path
-    const int32_t pod_top = top.get(root, "Pod", true);
-    // any other member that is an object or array was only bracket-checked: the whole body
-    // must be valid JSON, as for the Python verb (which answers 400 otherwise)
-    for (int32_t c = top.at(root).first; c >= 0; c = top.at(c).next) {
-      if (c == names || c == pod_top) continue;
-      if (top.is(c, json::Type::kObj) || top.is(c, json::Type::kArr)) {
-        if (!s.other.parse(top.raw(c))) return false;
-      }
+  // The body's top level only (Pod and NodeNames stay unparsed text), then the Pod on its own
+  // (`d`); the node-name list is parsed only when this worker has not seen that exact text.
+  if (!top.parse_shallow(body, 1) || !top.is(top.root(), json::Type::kObj)) return false;
+  const int32_t root = top.root();
+  const int32_t names = top.get(root, "NodeNames", true);
+  if (!top.is(names, json::Type::kArr)) return false;     // null / Nodes-only: Python path
+  const int32_t pod_top = top.get(root, "Pod", true);
+  // any other member that is an object or array was only bracket-checked: the whole body
+  // must be valid JSON, as for the Python verb (which answers 400 otherwise)
+  for (int32_t m = top.at(root).first; m >= 0; m = top.at(m).next) {
+    if (m == names || m == pod_top) continue;
+    if ((top.is(m, json::Type::kObj) || top.is(m, json::Type::kArr)) && !s.other.parse(top.raw(m))) return false;
+  }
+  c->raw_names = top.raw(names);
+  const bool has_pod_text = pod_top >= 0 && !top.is(pod_top, json::Type::kNull);
+  if (has_pod_text) c->pod_text = top.raw(pod_top);
+  c->reused = has_pod_text && last.valid && top.is(pod_top, json::Type::kObj) && c->pod_text == last.raw;
+  if (has_pod_text && !c->reused) {
+    if (!top.is(pod_top, json::Type::kObj) || !d.parse(c->pod_text)) return false;
+    c->pod = d.root();
+  }
+  return true;
+}
+
+// the pod's identity, completed flag and per-container demand; false: not a pod this verb reads
+static bool parse_pod(const json::Doc& d, int32_t pod, CachedPod& cached, Demand& dem, std::string_view* uid) {
+  if (!d.is(pod, json::Type::kObj)) return false;
+  const int32_t md = d.get(pod, "metadata");
+  if (md >= 0 && !d.is(md, json::Type::kNull)) {
+    if (!d.is(md, json::Type::kObj)) return false;
+    const int32_t u = d.get(md, "uid");
+    if (u >= 0) {
+      if (!d.is(u, json::Type::kStr)) return false;
+      *uid = d.str(u);
     }
-    raw_names = top.raw(names);
-    has_pod_text = pod_top >= 0 && !top.is(pod_top, json::Type::kNull);
-    if (has_pod_text) pod_text = top.raw(pod_top);
-    reused = has_pod_text && last.valid && top.is(pod_top, json::Type::kObj) && pod_text == last.raw;
-    if (has_pod_text && !reused) {
-      if (!top.is(pod_top, json::Type::kObj) || !d.parse(pod_text)) return false;
-      pod = d.root();
+    const int32_t nm = d.get(md, "name"), ns = d.get(md, "namespace"), del = d.get(md, "deletionTimestamp");
+    if (d.is(nm, json::Type::kStr)) cached.name.assign(d.str(nm));
+    cached.ns.assign(d.is(ns, json::Type::kStr) ? d.str(ns) : std::string_view("default"));
+    if (del >= 0 && !d.is(del, json::Type::kNull) && !(d.is(del, json::Type::kStr) && d.str(del).empty()))
+      cached.completed = true;
+  }
+  const int32_t stt = d.get(pod, "status");
+  if (d.is(stt, json::Type::kObj)) {
+    const int32_t ph = d.get(stt, "phase");
+    if (d.is(ph, json::Type::kStr) && (d.str(ph) == "Succeeded" || d.str(ph) == "Failed")) cached.completed = true;
+  }
+  const int32_t spec = d.get(pod, "spec");
+  int32_t cons = -1;
+  if (spec >= 0 && !d.is(spec, json::Type::kNull)) {
+    if (!d.is(spec, json::Type::kObj)) return false;
+    cons = d.get(spec, "containers");
+  }
+  if (cons < 0 || d.is(cons, json::Type::kNull)) return true;
+  if (!d.is(cons, json::Type::kArr)) return false;
+  if (d.at(cons).count > kMaxContainers) return false;
+  for (int32_t c = d.at(cons).first; c >= 0; c = d.at(c).next) {
+    if (!d.is(c, json::Type::kObj)) return false;
+    ContainerDemand& cd = dem.c[dem.n++];
+    const int32_t cn = d.get(c, "name");
+    cached.containers.emplace_back(d.is(cn, json::Type::kStr) ? d.str(cn) : std::string_view());
+    const int32_t res = d.get(c, "resources");
+    int32_t lim = -1;
+    if (res >= 0 && !d.is(res, json::Type::kNull)) {
+      if (!d.is(res, json::Type::kObj)) return false;
+      lim = d.get(res, "limits");
+    }
+    if (lim < 0 || d.is(lim, json::Type::kNull)) continue;
+    if (!d.is(lim, json::Type::kObj)) return false;
+    for (int k = 0; k < 2; ++k) {
+      const int32_t q = d.get(lim, k == 0 ? kPercent : kMemory);
+      if (q < 0 || d.is(q, json::Type::kNull)) continue;
+      if (!d.is(q, json::Type::kStr) && !d.is(q, json::Type::kNum)) return false;
+      int64_t v;
+      if (!quantity_value(d.str(q), k == 1, &v)) return false;  // Python logs + treats as 0
+      if (k == 0 && v > INT32_MAX) return false;
+      if (k == 0) cd.pct = static_cast<int32_t>(v);
+      else cd.mib = v;
     }
   }
-  Demand dem;
+  return true;
+}
+
+// nano-gpu/memory-bound: "true" (every container) or a comma list of container names. With no annotation, a
+// pod whose controlling owner was measured streaming (Ledger stream owners, nanogpu.telemetry.poller.OwnerLearner)
+// counts as memory-bound; "false" opts out. Marks the annotated containers, notes the owner; true: annotated.
+static bool mark_memory_bound(const json::Doc& d, int32_t pod, CachedPod* cached, Demand* dem) {
+  const int32_t md = d.get(pod, "metadata");
+  const int32_t ann = d.is(md, json::Type::kObj) ? d.get(md, "annotations") : -1;
+  const int32_t mb = d.is(ann, json::Type::kObj) ? d.get(ann, kMemBoundAnnotation) : -1;
+  if (d.is(mb, json::Type::kStr)) {
+    const std::string_view v = d.str(mb);
+    for (int c = 0; c < dem->n; ++c)
+      if (v == "true" || list_has(v, cached->containers[c])) dem->c[c].flags |= kFlagMemBound;
+  }
+  if (d.is(md, json::Type::kObj)) {
+    const std::string_view owner = controller_uid(d, d.get(md, "ownerReferences"));
+    if (!owner.empty()) cached->owner = owner_hash(owner);
+  }
+  return d.is(mb, json::Type::kStr);
+}
+
+// The pod's identity and demand: parsed, or the last pod's when the text is the same.
+bool Frontend::read_pod(VerbScratch& s, VerbCall* c) {
+  const json::Doc& d = s.d;
+  LastPod& last = s.last;
+  Demand& dem = c->dem;
   std::memset(&dem, 0, sizeof(dem));
-  std::string_view uid;
   // the pod's identity and containers are parsed into the last-pod record itself (its strings
   // keep their capacity); it is valid again only once the parse succeeded with a UID
   CachedPod& cached = last.cached;
   bool mb_annotated = false;
-  if (reused) {
+  if (c->reused) {
     dem = last.dem;
-    uid = last.uid;
+    c->uid = last.uid;
     mb_annotated = last.mb_annotated;
   } else {
+    const int32_t pod = c->pod;
     last.valid = false;
     cached.ns.clear();
     cached.name.clear();
     cached.containers.clear();
     cached.completed = false;
     cached.owner = 0;
-    if (pod >= 0 && !d.is(pod, json::Type::kNull)) {
-      if (!d.is(pod, json::Type::kObj)) return false;
-      const int32_t md = d.get(pod, "metadata");
-      if (md >= 0 && !d.is(md, json::Type::kNull)) {
-        if (!d.is(md, json::Type::kObj)) return false;
-        const int32_t u = d.get(md, "uid");
-        if (u >= 0) {
-          if (!d.is(u, json::Type::kStr)) return false;
-          uid = d.str(u);
-        }
-        const int32_t nm = d.get(md, "name"), ns = d.get(md, "namespace"), del = d.get(md, "deletionTimestamp");
-        if (d.is(nm, json::Type::kStr)) cached.name.assign(d.str(nm));
-        cached.ns.assign(d.is(ns, json::Type::kStr) ? d.str(ns) : std::string_view("default"));
-        if (del >= 0 && !d.is(del, json::Type::kNull) && !(d.is(del, json::Type::kStr) && d.str(del).empty()))
-          cached.completed = true;
-      }
-      const int32_t stt = d.get(pod, "status");
-      if (d.is(stt, json::Type::kObj)) {
-        const int32_t ph = d.get(stt, "phase");
-        if (d.is(ph, json::Type::kStr) && (d.str(ph) == "Succeeded" || d.str(ph) == "Failed")) cached.completed = true;
-      }
-      const int32_t spec = d.get(pod, "spec");
-      int32_t cons = -1;
-      if (spec >= 0 && !d.is(spec, json::Type::kNull)) {
-        if (!d.is(spec, json::Type::kObj)) return false;
-        cons = d.get(spec, "containers");
-      }
-      if (cons >= 0 && !d.is(cons, json::Type::kNull)) {
-        if (!d.is(cons, json::Type::kArr)) return false;
-        if (d.at(cons).count > kMaxContainers) return false;
-        for (int32_t c = d.at(cons).first; c >= 0; c = d.at(c).next) {
-          if (!d.is(c, json::Type::kObj)) return false;
-          ContainerDemand& cd = dem.c[dem.n++];
-          const int32_t cn = d.get(c, "name");
-          cached.containers.emplace_back(d.is(cn, json::Type::kStr) ? d.str(cn) : std::string_view());
-          const int32_t res = d.get(c, "resources");
-          int32_t lim = -1;
-          if (res >= 0 && !d.is(res, json::Type::kNull)) {
-            if (!d.is(res, json::Type::kObj)) return false;
-            lim = d.get(res, "limits");
-          }
-          if (lim >= 0 && !d.is(lim, json::Type::kNull)) {
-            if (!d.is(lim, json::Type::kObj)) return false;
-            for (int k = 0; k < 2; ++k) {
-              const int32_t q = d.get(lim, k == 0 ? kPercent : kMemory);
-              if (q < 0 || d.is(q, json::Type::kNull)) continue;
-              if (!d.is(q, json::Type::kStr) && !d.is(q, json::Type::kNum)) return false;
-              int64_t v;
-              if (!quantity_value(d.str(q), k == 1, &v)) return false;  // Python logs + treats as 0
-              if (k == 0) {
-                if (v > INT32_MAX) return false;
-                cd.pct = static_cast<int32_t>(v);
-              } else {
-                cd.mib = v;
-              }
-            }
-          }
-        }
-      }
-    }
-    // nano-gpu/memory-bound: "true" (every container) or a comma list of container names. With
-    // no annotation, a pod whose controlling owner was measured streaming (Ledger stream owners,
-    // nanogpu.telemetry.poller.OwnerLearner) counts as memory-bound; "false" opts out.
-    if (pod >= 0 && d.is(pod, json::Type::kObj)) {
-      const int32_t md = d.get(pod, "metadata");
-      const int32_t ann = d.is(md, json::Type::kObj) ? d.get(md, "annotations") : -1;
-      const int32_t mb = d.is(ann, json::Type::kObj) ? d.get(ann, kMemBoundAnnotation) : -1;
-      if (d.is(mb, json::Type::kStr)) {
-        const std::string_view v = d.str(mb);
-        for (int c = 0; c < dem.n; ++c)
-          if (v == "true" || list_has(v, cached.containers[c])) dem.c[c].flags |= kFlagMemBound;
-      }
-      if (d.is(md, json::Type::kObj)) {
-        const std::string_view owner = controller_uid(d, d.get(md, "ownerReferences"));
-        if (!owner.empty()) cached.owner = owner_hash(owner);
-      }
-      mb_annotated = d.is(mb, json::Type::kStr);
-    }
-    if (pod >= 0 && !uid.empty()) {
-      last.raw.assign(pod_text);
-      last.uid.assign(uid);
+    if (pod >= 0 && !d.is(pod, json::Type::kNull) && !parse_pod(d, pod, cached, dem, &c->uid)) return false;
+    if (pod >= 0 && d.is(pod, json::Type::kObj)) mb_annotated = mark_memory_bound(d, pod, &cached, &dem);
+    if (pod >= 0 && !c->uid.empty()) {
+      last.raw.assign(c->pod_text);
+      last.uid.assign(c->uid);
       last.dem = dem;
       last.mb_annotated = mb_annotated;
       last.valid = true;
-      uid = last.uid;   // `d` is reparsed by the next request; the uid outlives it here
+      c->uid = last.uid;   // `d` is reparsed by the next request; the uid outlives it here
     }
   }
   // A learned streaming owner marks an unannotated pod memory-bound. Read per request, not
@@ -2057,94 +2069,87 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
   // flag. The bind then adopts the priorities-time nomination, whose plan and demand the ledger
   // keeps (Ledger::reserve), so the pod lands where it was scored
   // (tests/test_frontend.py::test_owner_learned_between_priorities_and_bind_is_tolerated).
-  {
-    const uint64_t owner = reused ? last.cached.owner : cached.owner;
-    if (!mb_annotated && owner && ledger_->is_stream_owner(owner))
-      for (int c = 0; c < dem.n; ++c) dem.c[c].flags |= kFlagMemBound;
-  }
-  // node ids: any unknown node goes to Python, which can register it from its informer.
-  // kube-scheduler sends the same node list over and over, so each worker remembers the ids
-  // of the last lists it resolved (keyed by the array's raw text) and only checks that slot
-  // `id` still carries that name; a miss falls back to the ledger's name index.
-  io_end(kFeVerbPod, io0);
-  io0 = io_t0();
-  const uint64_t epoch = ledger_->node_epoch();
-  int slot = scanned ? -1 : framed && found != -2 ? found : idc.find(raw_names);
-  // a list's names are read through its token offsets into this request's text (no per-request
-  // copy of 2 x N views); only a list in another shape fills nv / nraw
-  const std::vector<std::pair<uint32_t, uint32_t>>* toks = nullptr;
-  // a prepared priorities answer is about one cached list as it stood (its stamp, its ids)
-  const uint64_t used_before = slot >= 0 ? idc.used[slot] : 0;
-  const bool ids_current = slot >= 0 && idc.epoch[slot] == epoch;
-  if (slot >= 0) {
-    // the same list text as before: its tokens sit at the same offsets (escape-free lists
-    // only are cached); names and ids come from the cache
-    toks = &idc.tok[slot];
-  } else {
-    // the common shape first, scanned directly: ["a","b",...] with no escapes; anything else
-    // (whitespace, escapes, other types) goes through the JSON parser
-    if (!scanned) s.ntok.clear();
-    const bool compact = scanned || scan_string_array(raw_names, &s.ntok);
-    bool plain = compact;
-    if (!plain) {
-      nv.clear();
-      nraw.clear();
-      json::Doc& dn = s.dn;
-      if (!dn.parse(raw_names) || !dn.is(dn.root(), json::Type::kArr)) return false;
-      plain = true;
-      for (int32_t c = dn.at(dn.root()).first; c >= 0; c = dn.at(c).next) {
-        if (!dn.is(c, json::Type::kStr)) return false;
-        nv.push_back(dn.str(c));
-        // the token is reused as written unless it holds an escape (then it is re-quoted, so
-        // the reply stays byte-identical to the Python verb's json.dumps)
-        const std::string_view tok = dn.raw(c);
-        if (tok.size() == nv.back().size() + 2) {
-          nraw.push_back(tok);
-        } else {
-          plain = false;
-          std::deque<std::string>& requoted = s.requoted;   // stable storage for this request
-          if (nraw.empty()) requoted.clear();
-          requoted.emplace_back();
-          json::append_quoted(&requoted.back(), nv.back());
-          nraw.push_back(requoted.back());
-        }
+  if (!mb_annotated && cached.owner && ledger_->is_stream_owner(cached.owner))
+    for (int k = 0; k < dem.n; ++k) dem.c[k].flags |= kFlagMemBound;
+  return true;
+}
+
+// A list not in the cache, parsed into the slot used longest ago (returned; -1: not a list of strings,
+// nothing changed). One with escapes leaves the slot invalid, its names in s.nv, its tokens re-quoted in s.nraw.
+static int fill_list_slot(Frontend::VerbScratch& s, std::string_view raw_names, bool scanned) {
+  IdCache& idc = s.idc;
+  std::vector<std::string_view>& nv = s.nv;
+  std::vector<std::string_view>& nraw = s.nraw;
+  // the common shape first, scanned directly: ["a","b",...] with no escapes; anything else
+  // (whitespace, escapes, other types) goes through the JSON parser
+  if (!scanned) s.ntok.clear();
+  const bool compact = scanned || scan_string_array(raw_names, &s.ntok);
+  bool plain = compact;
+  if (!plain) {
+    nv.clear();
+    nraw.clear();
+    json::Doc& dn = s.dn;
+    if (!dn.parse(raw_names) || !dn.is(dn.root(), json::Type::kArr)) return -1;
+    plain = true;
+    for (int32_t c = dn.at(dn.root()).first; c >= 0; c = dn.at(c).next) {
+      if (!dn.is(c, json::Type::kStr)) return -1;
+      nv.push_back(dn.str(c));
+      // the token is reused as written unless it holds an escape (then it is re-quoted, so
+      // the reply stays byte-identical to the Python verb's json.dumps)
+      const std::string_view tok = dn.raw(c);
+      if (tok.size() == nv.back().size() + 2) {
+        nraw.push_back(tok);
+      } else {
+        plain = false;
+        std::deque<std::string>& requoted = s.requoted;   // stable storage for this request
+        if (nraw.empty()) requoted.clear();
+        requoted.emplace_back();
+        json::append_quoted(&requoted.back(), nv.back());
+        nraw.push_back(requoted.back());
       }
     }
-    slot = 0;
-    for (int k = 1; k < kListSlots; ++k)
-      if (idc.used[k] < idc.used[slot]) slot = k;
-    idc.valid[slot] = plain;   // a list with escapes is parsed every time
-    idc.len[slot] = raw_names.size();
-    if (plain) idc.text[slot].assign(raw_names.data(), raw_names.size());
-    else idc.text[slot].clear();
-    idc.epoch[slot] = 0;                // ids checked below
-    if (compact) {
-      idc.tok[slot].swap(s.ntok);       // the scan's tokens become the slot's (no copy)
-      idc.compact[slot] = true;
-    } else {
-      idc.tok[slot].clear();
-      size_t joined = nraw.empty() ? 2 : 1 + nraw.size();   // brackets and commas
-      if (plain)
-        for (const std::string_view t : nraw) {
-          idc.tok[slot].emplace_back(static_cast<uint32_t>(t.data() - raw_names.data()), static_cast<uint32_t>(t.size()));
-          joined += t.size();
-        }
-      idc.compact[slot] = plain && joined == raw_names.size();
-    }
-    idc.ids[slot].assign(plain ? idc.tok[slot].size() : nv.size(), -1);
-    if (plain) toks = &idc.tok[slot];   // names through the slot's offsets from here on
   }
+  int slot = 0;
+  for (int k = 1; k < kListSlots; ++k)
+    if (idc.used[k] < idc.used[slot]) slot = k;
+  idc.valid[slot] = plain;   // a list with escapes is parsed every time
+  idc.len[slot] = raw_names.size();
+  if (plain) idc.text[slot].assign(raw_names.data(), raw_names.size());
+  else idc.text[slot].clear();
+  idc.epoch[slot] = 0;                // ids checked by the caller
+  if (compact) {
+    idc.tok[slot].swap(s.ntok);       // the scan's tokens become the slot's (no copy)
+    idc.compact[slot] = true;
+  } else {
+    idc.tok[slot].clear();
+    size_t joined = nraw.empty() ? 2 : 1 + nraw.size();   // brackets and commas
+    if (plain)
+      for (const std::string_view t : nraw) {
+        idc.tok[slot].emplace_back(static_cast<uint32_t>(t.data() - raw_names.data()), static_cast<uint32_t>(t.size()));
+        joined += t.size();
+      }
+    idc.compact[slot] = plain && joined == raw_names.size();
+  }
+  idc.ids[slot].assign(plain ? idc.tok[slot].size() : nv.size(), -1);
+  return slot;
+}
+
+// The list's cache slot, its names and its node ids.
+bool Frontend::resolve_list(VerbScratch& s, VerbCall* c) {
+  IdCache& idc = s.idc;
+  // kube-scheduler sends the same node list over and over, so each worker remembers the ids
+  // of the last lists it resolved (keyed by the array's raw text)
+  const uint64_t epoch = c->node_epoch = ledger_->node_epoch();
+  int slot = c->found != -2 ? c->found : idc.find(c->raw_names);
+  c->used_before = slot >= 0 ? idc.used[slot] : 0;
+  c->ids_current = slot >= 0 && idc.epoch[slot] == epoch;
+  if (slot < 0 && (slot = fill_list_slot(s, c->raw_names, c->found == -1)) < 0) return false;
+  // a valid slot holds the same list text as this request (only escape-free lists are cached):
+  // its tokens sit at the same offsets, so the names are read through them
+  c->names = NameToks{c->raw_names, idc.valid[slot] ? &idc.tok[slot] : nullptr, &s.nraw, &s.nv};
   idc.used[slot] = ++idc.clock;
   idc.mru = slot;
-  auto raw_at = [&](size_t i) -> std::string_view {
-    return toks ? raw_names.substr((*toks)[i].first, (*toks)[i].second) : nraw[i];
-  };
-  auto name_at = [&](size_t i) -> std::string_view {
-    if (!toks) return nv[i];
-    const auto& t = (*toks)[i];
-    return raw_names.substr(t.first + 1, t.second - 2);
-  };
-  const int32_t nn = static_cast<int32_t>(toks ? toks->size() : nv.size());
+  c->slot = slot;
   // node ids: any unknown node goes to Python, which can register it from its informer. The
   // ids of a cached list are re-checked (slot `id` still carries that name, else the ledger's
   // name index) only when a node was added or removed since (the ledger's epoch moved).
@@ -2156,8 +2161,8 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
     NameTable& nid = s.nid;
     if (nid.owner != serial_ || nid.epoch != epoch) nid.reset(serial_, epoch);
     int32_t prev = -1;
-    for (size_t i = 0; i < static_cast<size_t>(nn); ++i) {
-      const std::string_view name = name_at(i);
+    for (size_t i = 0; i < ids.size(); ++i) {
+      const std::string_view name = c->names.name_at(i);
       // the successor of the previous name last time, else the table (its own copy of every
       // name in a compact arena): a hit touches neither the ledger's node slots nor its lock,
       // and is exact (names compared, not only hashed)
@@ -2179,35 +2184,37 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
     }
     idc.epoch[slot] = epoch;
   }
-  // the options as of the last policy change this worker saw (one atomic load a request; the
-  // lock and the copy only after a change)
-  if (s.opt_seen != opt_version_.load(std::memory_order_acquire) || s.opt_owner != serial_) {
-    std::lock_guard<std::mutex> g(opt_mu_);
-    s.opt = opt_;
-    s.normalize = normalize_;
-    s.nominate = nominate_;
-    s.decisive = decisive_;
-    s.lead = lead_;
-    s.opt_owner = serial_;   // a thread_local scratch serves every Frontend of its thread
-    s.opt_seen = opt_version_.load(std::memory_order_relaxed);
-  }
-  const Options& o = s.opt;
-  const bool normalize = s.normalize, nominate = s.nominate, decisive = s.decisive && !o.compat;
-  io_end(kFeVerbNames, io0);
-  // a nomination another worker left for after its answer is made before this verb reads the
-  // ledger (this worker's own ran before it read this request); bounded
-  if (nominate && ledger_->attached() > 1) ledger_->wait_deferred_nominations(kDeferredNominationWaitNs);
-  io0 = io_t0();
+  return true;
+}
+
+// the options as of the last policy change this worker saw (one atomic load a request; the
+// lock and the copy only after a change)
+void Frontend::refresh_options(VerbScratch& s) {
+  if (s.opt_seen == opt_version_.load(std::memory_order_acquire) && s.opt_owner == serial_) return;
+  std::lock_guard<std::mutex> g(opt_mu_);
+  s.opt = opt_;
+  s.normalize = normalize_;
+  s.nominate = nominate_;
+  s.decisive = decisive_;
+  s.lead = lead_;
+  s.opt_owner = serial_;   // a thread_local scratch serves every Frontend of its thread
+  s.opt_seen = opt_version_.load(std::memory_order_relaxed);
+}
+
+// The pod's own nomination dropped, then the pod cached for its bind (now, or after the answer).
+void Frontend::drop_and_cache(VerbScratch& s, const VerbCall& c, bool prioritize) {
+  const LastPod& last = s.last;
+  const std::string_view uid = c.uid;
   // not against itself; priorities right behind this worker's filter of the same pod text
   // (`reused`) with no nomination made anywhere since find it dropped already: no second trip
   // to the pod table
-  if (nominate && !uid.empty() &&
-      !(prioritize && reused && s.nom_dropped && ledger_->nominations_made() == s.nom_mark)) {
+  if (s.nominate && !uid.empty() &&
+      !(prioritize && c.reused && s.nom_dropped && ledger_->nominations_made() == s.nom_mark)) {
     s.nom_mark = ledger_->nominations_made();
     ledger_->drop_nomination(uid);
-    s.nom_dropped = reused || (pod >= 0 && last.valid);   // about the pod `last` holds
+    s.nom_dropped = c.reused || (c.pod >= 0 && last.valid);   // about the pod `last` holds
   }
-  if ((pod >= 0 || reused) && !uid.empty() && !(prioritize && has_pod(uid))) {
+  if ((c.pod >= 0 || c.reused) && !uid.empty() && !(prioritize && has_pod(uid))) {
     // filter caches the pod for its bind (and, with other worker processes on the ledger,
     // publishes it for their binds); priorities of the same cycle find it there. After the
     // answer with one worker thread: the pod's own bind is the only reader, and it follows the
@@ -2215,175 +2222,170 @@ bool Frontend::filter_verb(std::string_view body, bool prioritize, std::string* 
     // for it (prepare_bind, kHandoffWaitNs); one on this thread comes after it
     if (s.defer_cache && last.valid && uid.data() == last.uid.data()) {
       s.defer_put = true;   // the pod is last.raw / last.uid / last.cached: stable until the next request
-      s.defer_dem = dem;
+      s.defer_dem = c.dem;
     } else {
-      cache_pod(s, uid, cached, reused ? std::string_view(last.raw) : d.raw(pod), dem);
+      cache_pod(s, uid, last.cached, c.reused ? std::string_view(last.raw) : s.d.raw(c.pod), c.dem);
     }
   }
+}
+
+// The filter's placements, the node it nominates, its reply, and what it leaves for run_deferred.
+void Frontend::filter_answer(VerbScratch& s, const VerbCall& c, std::string* out) {
+  const std::vector<int32_t>& ids = s.idc.ids[c.slot];
+  std::vector<int32_t>& rcs = s.rcs;
+  std::vector<int32_t>& scores = s.scores;
+  const Options& o = s.opt;
+  const Demand& dem = c.dem;
+  const std::string_view uid = c.uid;
+  const bool decisive = s.decisive && !o.compat;
+  rcs.resize(ids.size());
+  scores.resize(ids.size());
+  {
+    IoTimer it{kFeVerbAssume};
+    const uint64_t epoch0 = ledger_->epoch();
+    ledger_->assume_many(ids.data(), static_cast<int>(ids.size()), dem, o, rcs.data(), scores.data());
+    VerbScratch::LastAssume& la = s.last_assume;
+    la.valid = !uid.empty();
+    if (la.valid) {
+      la.epoch = epoch0;
+      la.dem_hash = dem.hash();
+      la.opt_seen = s.opt_seen;
+      la.uid.assign(uid);
+      la.ids.assign(ids.begin(), ids.end());
+      la.rcs.assign(rcs.begin(), rcs.end());
+      la.scores.assign(scores.begin(), scores.end());
+      if (s.ahead) s.remember_class(dem, la.dem_hash);
+    }
+  }
+  // decisive: the node priorities would rank first is the only one answered (and nominated)
+  const int64_t pick = decisive ? top_pick(scores, rcs, uid) : -1;
+  // one fitting node: kube-scheduler binds it without a priorities call, so the filter
+  // nominates it (otherwise the pod is invisible to the next filters until its bind reserves)
+  int64_t only = -1;
+  if (!decisive && s.nominate && !o.compat) {
+    const auto a = std::find(rcs.begin(), rcs.end(), kOk);
+    if (a != rcs.end() && std::find(a + 1, rcs.end(), kOk) == rcs.end()) only = a - rcs.begin();
+  }
+  const int64_t nom = pick >= 0 ? pick : only;
+  if (nom >= 0 && s.nominate && !uid.empty() && wants_devices(dem)) nominate_or_defer(s, ids[nom], uid, dem);
+  const bool any_failed = write_filter_reply(s, c, pick, out);
+  s.prep.valid = false;   // a prepared answer belongs to the latest filter
+  if (pick < 0) arrange_deferred(s, c, any_failed, decisive);
+}
+
+// the reply over s.rcs: the fitting nodes (or the pick alone), a reason per other; true: some did not fit
+bool Frontend::write_filter_reply(VerbScratch& s, const VerbCall& c, int64_t pick, std::string* out) {
+  const std::vector<int32_t>& rcs = s.rcs;
+  const NameToks& names = c.names;
+  const Demand& dem = c.dem;
   std::string& r = *out;
-  r.reserve(64 + 128 * static_cast<size_t>(nn));   // room for a FailedNodes entry per node
-  if (!prioritize) {
-    rcs.resize(ids.size());
-    scores.resize(ids.size());
-    io_end(kFeVerbCache, io0);
-    {
-      IoTimer it{kFeVerbAssume};
-      const uint64_t epoch0 = ledger_->epoch();
-      ledger_->assume_many(ids.data(), static_cast<int>(ids.size()), dem, o, rcs.data(), scores.data());
-      VerbScratch::LastAssume& la = s.last_assume;
-      la.valid = !uid.empty();
-      if (la.valid) {
-        la.epoch = epoch0;
-        la.dem_hash = dem.hash();
-        la.opt_seen = s.opt_seen;
-        la.uid.assign(uid);
-        la.ids.assign(ids.begin(), ids.end());
-        la.rcs.assign(rcs.begin(), rcs.end());
-        la.scores.assign(scores.begin(), scores.end());
-        if (s.ahead) s.remember_class(dem, la.dem_hash);
-      }
+  // written straight into the reply; a fitting node's name is its request token, as is
+  r.clear();
+  r += "{\"Nodes\":null,\"NodeNames\":";
+  const bool any_failed = std::any_of(rcs.begin(), rcs.end(), [](int32_t rc) { return rc != kOk; });
+  bool first = true;
+  if (pick >= 0) {
+    r += '[';
+    r += names.raw_at(static_cast<size_t>(pick));
+    r += ']';
+  } else if (!any_failed && names.toks && s.idc.compact[c.slot]) {
+    r += c.raw_names;   // every node fits: the request's own list is the answer
+  } else {
+    r += '[';
+    for (size_t i = 0; i < rcs.size(); ++i) {
+      if (rcs[i] != kOk) continue;
+      if (!first) r += ',';
+      r += names.raw_at(i);
+      first = false;
     }
-    // decisive: the node priorities would rank first is the only one answered (and nominated)
-    const int64_t pick = decisive ? top_pick(scores, rcs, uid) : -1;
-    // one fitting node: kube-scheduler binds it without a priorities call, so the filter
-    // nominates it (otherwise the pod is invisible to the next filters until its bind reserves)
-    int64_t only = -1;
-    if (!decisive && nominate && !o.compat) {
-      for (size_t i = 0; i < ids.size(); ++i) {
-        if (rcs[i] != kOk) continue;
-        if (only >= 0) {
-          only = -1;
-          break;
-        }
-        only = static_cast<int64_t>(i);
-      }
-    }
-    const int64_t nom = pick >= 0 ? pick : only;
-    if (nom >= 0 && nominate && !uid.empty() && wants_devices(dem)) {
-      if (s.defer && defer_nominate_ok(s) && last.valid && uid.data() == last.uid.data()) {
-        s.defer_nominate = true;
-        s.defer_node = ids[nom];
-        s.defer_dem = dem;
-        ledger_->deferred_nomination_begin();   // other workers' filters wait for it
-      } else {
-        IoTimer it{kFeVerbNominate};
-        ledger_->nominate(ids[nom], uid, dem, o);
-        s.node_changed(ids[nom]);
-      }
-      s.nom_dropped = false;
-    }
-    // written straight into the reply; a fitting node's name is its request token, as is
-    r.clear();
-    r += "{\"Nodes\":null,\"NodeNames\":";
-    bool any_failed = false;
-    for (size_t i = 0; i < ids.size() && !any_failed; ++i) any_failed = rcs[i] != kOk;
-    bool first = true;
-    if (pick >= 0) {
-      r += '[';
-      r += raw_at(static_cast<size_t>(pick));
-      r += ']';
-    } else if (!any_failed && toks && idc.compact[slot]) {
-      r += raw_names;   // every node fits: the request's own list is the answer
-    } else {
-      r += '[';
-      for (size_t i = 0; i < ids.size(); ++i) {
-        if (rcs[i] != kOk) continue;
-        if (!first) r += ',';
-        r += raw_at(i);
-        first = false;
-      }
-      r += ']';
-    }
-    r += ",\"FailedNodes\":{";
-    if (any_failed) {
-      // "can't allocate <demand> on node <name>: <reason>" per failing node, written in place:
-      // the demand text, the reasons (alloc.cpp err_str) and an escape-free name (its request
-      // token is the name in quotes) need no escaping
-      std::string& dstr = s.dstr;
-      dstr.clear();
-      char num[24];
-      for (int i = 0; i < dem.n; ++i) {
-        dstr += '(';
-        dstr.append(num, static_cast<size_t>(std::to_chars(num, num + sizeof num, dem.c[i].pct).ptr - num));
-        if (dem.c[i].mib) {
-          dstr += ',';
-          dstr.append(num, static_cast<size_t>(std::to_chars(num, num + sizeof num, dem.c[i].mib).ptr - num));
-          dstr += "Mi";
-        }
-        dstr += ')';
-      }
-      first = true;
-      for (size_t i = 0; i < ids.size(); ++i) {
-        if (rcs[i] == kOk) continue;
-        if (!first) r += ',';
-        const std::string_view tok = raw_at(i), name = name_at(i);
-        r += tok;
-        if (tok.size() == name.size() + 2) {
-          r += ":\"can't allocate ";
-          r += dstr;
-          r += " on node ";
-          r += name;
-          r += ": ";
-          r += err_str(rcs[i]);
-          r += '"';
-        } else {
-          r += ':';
-          json::append_quoted(&r, "can't allocate " + dstr + " on node " + std::string(name) + ": " + err_str(rcs[i]));
-        }
-        first = false;
-      }
-    }
-    r += "},\"Error\":\"\"}";
-    s.prep.valid = false;   // a prepared answer belongs to the latest filter
-    if (pick < 0 && slot >= 0 && idc.valid[slot] && idc.epoch[slot] == epoch) {
-      size_t n_ok = rcs.size();
-      if (any_failed) {
-        n_ok = 0;
-        for (const int32_t rc : rcs) n_ok += rc == kOk;
-      }
-      if (n_ok > 1) {   // one node: kube-scheduler skips priorities
-        if (any_failed) {
-          if (s.defer) s.defer_list = slot;
-          else idc.remember_subset(slot, rcs);
-        }
-        // the priorities call that follows is answered behind this answer (run_deferred), over
-        // this list or its fitting subset
-        if (s.prepare && !decisive && s.last_assume.valid && last.valid && uid.data() == last.uid.data()) {
-          s.prep_want = true;
-          s.prep_slot = any_failed ? -1 : slot;
-          s.prep_dem = dem;
-        }
-      }
-    }
-    return true;
+    r += ']';
   }
-  NameToks names;
-  names.text = raw_names;
-  names.toks = toks;
-  names.nraw = &nraw;
+  r += ",\"FailedNodes\":{";
+  if (any_failed) {
+    // "can't allocate <demand> on node <name>: <reason>" per failing node, written in place:
+    // the demand text, the reasons (alloc.cpp err_str) and an escape-free name (its request
+    // token is the name in quotes) need no escaping
+    std::string& dstr = s.dstr;
+    dstr.clear();
+    char num[24];
+    for (int i = 0; i < dem.n; ++i) {
+      dstr += '(';
+      dstr.append(num, static_cast<size_t>(std::to_chars(num, num + sizeof num, dem.c[i].pct).ptr - num));
+      if (dem.c[i].mib) {
+        dstr += ',';
+        dstr.append(num, static_cast<size_t>(std::to_chars(num, num + sizeof num, dem.c[i].mib).ptr - num));
+        dstr += "Mi";
+      }
+      dstr += ')';
+    }
+    first = true;
+    for (size_t i = 0; i < rcs.size(); ++i) {
+      if (rcs[i] == kOk) continue;
+      if (!first) r += ',';
+      const std::string_view tok = names.raw_at(i), name = names.name_at(i);
+      r += tok;
+      if (tok.size() == name.size() + 2) {
+        r += ":\"can't allocate ";
+        r += dstr;
+        r += " on node ";
+        r += name;
+        r += ": ";
+        r += err_str(rcs[i]);
+        r += '"';
+      } else {
+        r += ':';
+        json::append_quoted(&r, "can't allocate " + dstr + " on node " + std::string(name) + ": " + err_str(rcs[i]));
+      }
+      first = false;
+    }
+  }
+  r += "},\"Error\":\"\"}";
+  return any_failed;
+}
+
+// what a filter with several fitting nodes leaves for run_deferred: their list kept, priorities prepared
+void Frontend::arrange_deferred(VerbScratch& s, const VerbCall& c, bool any_failed, bool decisive) {
+  IdCache& idc = s.idc;
+  const int slot = c.slot;
+  if (!idc.valid[slot] || idc.epoch[slot] != c.node_epoch) return;
+  const size_t n_ok = any_failed ? static_cast<size_t>(std::count(s.rcs.begin(), s.rcs.end(), kOk)) : s.rcs.size();
+  if (n_ok <= 1) return;   // one node: kube-scheduler skips priorities
+  if (any_failed) {
+    if (s.defer) s.defer_list = slot;
+    else idc.remember_subset(slot, s.rcs);
+  }
+  // the priorities call that follows is answered behind this answer (run_deferred), over
+  // this list or its fitting subset
+  if (s.prepare && !decisive && s.last_assume.valid && s.last.valid && c.uid.data() == s.last.uid.data()) {
+    s.prep_want = true;
+    s.prep_slot = any_failed ? -1 : slot;
+    s.prep_dem = c.dem;
+  }
+}
+
+void Frontend::priorities(VerbScratch& s, const VerbCall& c, std::string* out) {
+  const std::vector<int32_t>& ids = s.idc.ids[c.slot];
   // the answer prepared behind this pod's filter answer, if all it was made of still reads the same
-  io_end(kFeVerbCache, io0);
   if (s.prep.valid) {
     VerbScratch::Prepared& p = s.prep;
     p.valid = false;   // one use
     const uint64_t a0 = io_t0();   // what is left of the placements on the path: this comparison
-    if (slot == p.slot && used_before == p.used && ids_current && p.opt_seen == s.opt_seen && uid == p.uid &&
-        p.dem_hash == dem.hash() && p.epoch == ledger_->epoch() && p.nom_made == ledger_->nominations_made() &&
+    if (c.slot == p.slot && c.used_before == p.used && c.ids_current && p.opt_seen == s.opt_seen && c.uid == p.uid &&
+        p.dem_hash == c.dem.hash() && p.epoch == ledger_->epoch() && p.nom_made == ledger_->nominations_made() &&
         p.margin == ledger_->nomination_margin()) {
       s.last_assume.valid = false;   // the placements it was made from: used
-      r.swap(p.body);
+      out->swap(p.body);
       io_end(kFeVerbAssume, a0);
-      if (p.node >= 0) nominate_for_priorities(s, p.node, uid, dem);
+      if (p.node >= 0) nominate_or_defer(s, p.node, c.uid, c.dem);
       prio_prepared_used.fetch_add(1, std::memory_order_relaxed);
-      return true;
+      return;
     }
     prio_prepared_stale.fetch_add(1, std::memory_order_relaxed);
   }
-  scores.resize(ids.size());
-  rcs.resize(ids.size());
-  const int32_t node = priorities_answer(s, uid, dem, ids, names, false, &r);
-  if (node >= 0) nominate_for_priorities(s, node, uid, dem);
-  return true;
+  s.scores.resize(ids.size());
+  s.rcs.resize(ids.size());
+  const int32_t node = priorities_answer(s, c.uid, c.dem, ids, c.names, false, out);
+  if (node >= 0) nominate_or_defer(s, node, c.uid, c.dem);
 }
 
 int32_t Frontend::priorities_answer(VerbScratch& s, std::string_view uid, const Demand& dem,
@@ -2394,14 +2396,12 @@ int32_t Frontend::priorities_answer(VerbScratch& s, std::string_view uid, const 
   const Options& o = s.opt;
   const bool normalize = s.normalize, nominate = s.nominate;
   std::string& r = *out;
-  {
-    const uint64_t a0 = reuse_only ? 0 : io_t0();   // (a prepared answer is timed whole, off the path)
-    if (!reuse_assume(s, uid, dem, ids, &rcs, &scores)) {
-      if (reuse_only) return -2;
-      ledger_->assume_many(ids.data(), static_cast<int>(ids.size()), dem, o, rcs.data(), scores.data());
-    }
-    io_end(kFeVerbAssume, a0);
+  const uint64_t a0 = reuse_only ? 0 : io_t0();   // (a prepared answer is timed whole, off the path)
+  if (!reuse_assume(s, uid, dem, ids, &rcs, &scores)) {
+    if (reuse_only) return -2;
+    ledger_->assume_many(ids.data(), static_cast<int>(ids.size()), dem, o, rcs.data(), scores.data());
   }
+  io_end(kFeVerbAssume, a0);
   int64_t best = -1;
   int n_best = 0;
   int32_t second = -1;   // best score among the other fitting nodes
@@ -2434,7 +2434,7 @@ int32_t Frontend::priorities_answer(VerbScratch& s, std::string_view uid, const 
     n_best = 1;
   }
   const bool lead = n_best == 1 && (second < 0 || scores[best] - second >= margin);
-  // (the nomination itself is the caller's to make: nominate_for_priorities, with the node returned)
+  // (the nomination itself is the caller's to make: nominate_or_defer, with the node returned)
   const bool nominated = nominate && lead && !uid.empty() && dem.n > 0 && wants_devices(dem);
   // The nomination is the pod's placement from this answer on: every later filter sees its
   // devices held. kube-scheduler adds its own score plugins (LeastAllocated, BalancedAllocation,
