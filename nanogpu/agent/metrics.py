@@ -184,6 +184,15 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
                 name, label, help_ = part.failed_metric
                 family(name, "gauge", help_, [(_labels(device=i, **{label: n}), len(p["failed"].get(n, [])))
                                               for i, p in ran for n in p["checked"]])
+        xcd = [(i, r["xcd"]) for i, r in reps if r.get("xcd")]     # only devices where the XCD check ran
+        family("nanogpu_selftest_xcd_checked", "gauge", "groups of the XCD check the last deep self-test ran on the device",
+               [(_labels(device=i), len(x["checked"])) for i, x in xcd])
+        family("nanogpu_selftest_xcd_failed_pairs", "gauge",
+               "ordered pairs (writer XCD, reader XCD) that failed the last deep self-test's XCD check, by group",
+               [(_labels(device=i, group=g), len(x["failed"].get(g, []))) for i, x in xcd for g in x["checked"]])
+        family("nanogpu_selftest_xcd_pairs_verified", "gauge",
+               "ordered pairs (writer XCD, reader XCD) the last deep self-test's XCD check verified",
+               [(_labels(device=i), x.get("pairs_verified", 0)) for i, x in xcd])
     if fence is not None:
         def per_device(key):
             return [(_labels(device=i), v) for i, v in sorted(fence.get(key, {}).items())]

@@ -140,7 +140,8 @@ class NodeAgent:
                  sysfs_root: str = "", kubelet_check_s: float = 1.0, pod_resources_socket: str | None = None,
                  reconcile_period_s: float = 5.0, selftest_deep: bool = False, selftest_hbm_mib: int = 0,
                  selftest_period_s: float = 0.0, selftest_paths=None, selftest_fence: int = 0,
-                 selftest_fence_reset: bool = False, selftest_valu=None, selftest_scalar=None, selftest_mem=None):
+                 selftest_fence_reset: bool = False, selftest_valu=None, selftest_scalar=None, selftest_mem=None,
+                 selftest_xcd=None):
         self.api = api
         self.node = node_name
         self.topo = topo
@@ -159,6 +160,12 @@ class NodeAgent:
         # what every deep sweep also runs of each optional part ("all", "a,b" or names); any of them makes the sweep deep
         self.selftest_parts = Selection.parse(paths=selftest_paths, valu=selftest_valu, scalar=selftest_scalar, mem=selftest_mem)
         if any(vars(self.selftest_parts).values()):
+            self.selftest_deep = True
+        from ..probe.selftest_xcd import parse_xcd
+
+        # the groups of the XCD check every deep run makes once, on the mask of the sweep; any makes the sweep deep
+        self.selftest_xcd = parse_xcd(selftest_xcd)
+        if self.selftest_xcd:
             self.selftest_deep = True
         self._no_paths_logged = False
         # > 0: a whole GPU whose deep sweep fails on CUs that fail again when swept alone loses the
@@ -414,7 +421,7 @@ class NodeAgent:
             if self.selftest_fence and self.plugin is not None and self._is_spx(i):
                 r, fenced_now = self._deep_fenced(P, i, bits, nbytes)
             else:
-                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, **vars(self.selftest_parts))
+                r = deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, xcd=self.selftest_xcd, **vars(self.selftest_parts))
             reports[i] = r
             if self.selftest_stats is None:
                 self.selftest_stats = {"reports": {}, "at": {}, "runs": {}}
@@ -430,7 +437,8 @@ class NodeAgent:
         """The deep test of whole GPU `i` in fence mode (`--selftest-fence`), on the executor's
         thread: (the report that decides the device, whether it proposes a new fence).
 
-        The sweep runs alone; only a clean chip (or what is usable of it) judges HBM. A failing
+        The sweep runs alone; only a clean chip (or what is usable of it) judges HBM and runs the XCD check
+        (`selftest_xcd`), which goes to the runs that get `hbm_bytes`. A failing
         sweep that names CUs (`fenceable`) is localised over the plan's units. When every failed
         CU failed again in a unit swept alone, and the device's fence stays within
         `selftest_fence` units, one verification run over the plan's bits less those units
@@ -443,7 +451,8 @@ class NodeAgent:
         select = vars(self.selftest_parts)
         sweep = deep_selftest(P, i, cu_mask_bits=bits, **select)
         if sweep.ok:
-            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, **select) if nbytes else sweep), False
+            more = nbytes or self.selftest_xcd
+            return (deep_selftest(P, i, cu_mask_bits=bits, hbm_bytes=nbytes, xcd=self.selftest_xcd, **select) if more else sweep), False
         if not fenceable(sweep):
             return sweep, False
         all_bits = bits if bits is not None else list(range(dc.cus))
@@ -460,7 +469,7 @@ class NodeAgent:
             log.warning("agent %s: device %d is not fenced: %s", self.node, i, why)
             return sweep, False
         verify = deep_selftest(P, i, cu_mask_bits=[b for b in all_bits if b // dc.unit not in bad],
-                               hbm_bytes=nbytes, **select)
+                               hbm_bytes=nbytes, xcd=self.selftest_xcd, **select)
         stray = sorted(set(verify.cu_keys) & failed_cus(sweep))
         if verify.ok and stray:
             verify.ok = False
@@ -576,7 +585,8 @@ class NodeAgent:
         masked to the units no tenant holds at this moment (`deep_plan`), so no tenant's CUs are
         touched; HBM is checked only on devices without a grant. A grant that arrives while a
         sweep is in flight shares its new CUs with the sweep until that one ends: 0.26 ms at
-        4 rounds, 1 ms at 16, measured on MI355X (profiles/gpu_calibration.md). Failures are sticky
+        4 rounds, 1 ms at 16, measured on MI355X (profiles/gpu_calibration.md); with `selftest_xcd` another 0.20 ms.
+        Failures are sticky
         until the agent restarts: this only ever adds to `selftest_failed`, and a later clean
         run clears nothing. Returns the devices that failed this run, or None when skipped."""
         plans = {i: self.deep_plan(i) for i in range(len(self.topo.devices))}
@@ -648,6 +658,10 @@ def build_parser():
     for part in PARTS:
         ap.add_argument(f"--selftest-{part.key}", action=_Names, const=part, default=[], metavar="all|LIST",
                         help=part.agent_help if part.listed else argparse.SUPPRESS)
+    from ..probe import selftest_xcd
+
+    # the XCD check's groups: a check of the device, no part, with the parts' flag action and wording
+    ap.add_argument("--selftest-xcd", action=_Names, const=selftest_xcd.FLAG, default=[], metavar="all|LIST", help=argparse.SUPPRESS)
 
     class _Fence(argparse.Action):             # --selftest-fence N > 0 implies --selftest-deep
         def __call__(self, parser, ns, values, option_string=None):
@@ -704,6 +718,7 @@ def main(argv: list[str] | None = None) -> int:
                           selftest_deep=a.selftest_deep, selftest_hbm_mib=a.selftest_hbm_mib,
                           selftest_period_s=a.selftest_period,
                           selftest_fence=a.selftest_fence, selftest_fence_reset=a.selftest_fence_reset,
+                          selftest_xcd=a.selftest_xcd,
                           **{name: getattr(a, name) for name in (f"selftest_{part.key}" for part in PARTS)})
         await agent.start()
         if a.selftest:

@@ -22,8 +22,15 @@ file) are further launches on the same mask after each sweep launch, with record
 `cu_sweep_mem` (`selftest_mem.py`: the CU's memory pipeline: global and buffer loads and stores, the L1, LDS forms,
 LDS-DMA, atomics), the last one.
 
+`xcd_check` (`selftest_xcd.py`, the keyword `xcd=`) is a check of the device like the HBM check, not a part: after
+the coverage loop and on the same mask it verifies on one XCD what another wrote, by a hand-off across a kernel
+boundary, by release, ticket and acquire inside one kernel, and by memory-side atomics onto shared words. A
+failure names a pair of XCDs, which no CU-mask fence can keep a tenant off.
+
 What it does not cover: HBM pages and CUs held by tenants (the agent sweeps only free units
-and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache, and of
+and checks HBM only on devices without a grant), the contents of L2 / Infinity Cache (whether a
+handed-off line was still in L2 at the kernel's end is not claimed, nor which XCD draws a last ticket; the
+write-through `sc1` forms of a hand-off are not run), and of
 the matrix unit the 16x16 shapes, the sparse (smfmac) forms, bf6 operands, mixed A / B formats
 and Inf and NaN operands.
 
@@ -32,7 +39,7 @@ runs `deep_selftest` once per candidate unit, masked to it, and says which units
 which failing CUs no such unit explains. The agent fences those units (`--selftest-fence`)
 instead of failing the device when `fenceable` allows it.
 
-`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--scalar all|LIST] [--mem all|LIST] [--json]`
+`python -m nanogpu.probe.selftest [--device N] [--hbm-mib M] [--paths all|LIST] [--valu all|LIST] [--scalar all|LIST] [--mem all|LIST] [--xcd all|LIST] [--json]`
 prints one report;
 with `--fence N` it also prints the units (at most N) an agent would fence, and changes nothing.
 """
@@ -42,7 +49,7 @@ import logging
 import time
 from dataclasses import asdict, dataclass, field, make_dataclass
 
-from . import selftest_common, selftest_mem, selftest_paths, selftest_scalar, selftest_valu
+from . import selftest_common, selftest_mem, selftest_paths, selftest_scalar, selftest_valu, selftest_xcd
 from .selftest_common import HI_MUL, M32, Part, by_cu, coverage, cu_key, mix32, or_all, simds_seen_min
 
 log = logging.getLogger(__name__)
@@ -127,12 +134,15 @@ class DeepReport:
     valu: dict | None = field(default=None, repr=False)
     scalar: dict | None = field(default=None, repr=False)
     mem: dict | None = field(default=None, repr=False)
+    xcd: dict | None = field(default=None, repr=False)       # selftest_xcd.run_xcd's; None: not run
 
     def to_dict(self) -> dict:
         """What /metrics and --json show: every field but `cu_keys`, as before that field existed;
-        a part that did not run only where its `Part` says so (`none_in_dict`)."""
+        a part that did not run only where its `Part` says so (`none_in_dict`), the XCD check only where it ran."""
         d = asdict(self)
         del d["cu_keys"]
+        if d["xcd"] is None:
+            del d["xcd"]
         for part in PARTS:
             if d[part.key] is None and not part.none_in_dict:
                 del d[part.key]
@@ -147,6 +157,8 @@ class DeepReport:
                  for f in (self.sweep or {}).get("failed", [])]
         for part, d in _part_reports(self):
             parts += part.clauses(d)
+        if self.xcd and not self.xcd.get("ok", True):
+            parts += selftest_xcd.clauses(self.xcd)
         if self.hbm and self.hbm.get("errors"):
             first = self.hbm.get("first") or []
             at = f", first at byte {first[0][0]} (expected {first[0][1]:#010x}, got {first[0][2]:#010x})" if first else ""
@@ -217,7 +229,7 @@ class Selection(make_dataclass("_PartFields", [(part.key, list, field(default_fa
 
 
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
-                  seed: int | None = None, rounds: int = 4, **select) -> DeepReport:
+                  seed: int | None = None, rounds: int = 4, xcd=None, **select) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
     the sweep to those CU-mask bits (the agent passes the units no tenant holds; None: the
     whole chip). `hbm_bytes` > 0 adds the pattern check of that much fresh memory, on a stream
@@ -227,11 +239,14 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
     (the matrix paths) makes the sweep launches its binding instead of `cu_sweep`: still one visit
     per CU. Every other selected part adds, after each sweep launch of the coverage loop, a launch
     of its binding on the same mask, in the order of `PARTS`. A part this probe has no binding for
-    gets a note and is not run. `ok` is false if and only if a CU failed a check or a name of a
-    part, HBM errors were counted, or HIP raised."""
+    gets a note and is not run. `xcd` (None, "all", "a,b" or a list of `selftest_xcd.GROUPS`) adds one `xcd_check`
+    after the coverage loop and before the HBM check, on the same mask, with `rounds` capped at 4; it is no part
+    of `select`, so `localise_failure`'s unit sweeps do not carry it. `ok` is false if and only if a CU failed a
+    check or a name of a part, the XCD check failed, HBM errors were counted, or HIP raised."""
     from ..agent import cumask
 
     names = vars(Selection.parse(**select))
+    xcd_names = selftest_xcd.parse_xcd(xcd)
     if seed is None:
         seed = int(time.time() * 1000) & M32   # another pattern every run
     rep = DeepReport(device=device, masked=cu_mask_bits is not None, seed=seed)
@@ -280,9 +295,14 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
                 rep.notes.append(part.note_unreached.format(n=f["cus_uncovered"]))
         if sweep["cus_uncovered"]:
             rep.notes.append(f"{sweep['cus_uncovered']} CUs not reached in {launches} launches")
+        if xcd_names and not hasattr(P, "xcd_check"):
+            rep.notes.append(selftest_xcd.NOTE_MISSING)
+        elif xcd_names:
+            rep.xcd = selftest_xcd.run_xcd(P, device, mask, rounds, seed, xcd_names)
+            rep.notes += selftest_xcd.notes(rep.xcd)
         if hbm_bytes > 0:
             rep.hbm = _hbm_check(P, device, hbm_bytes, seed, mask, rep.notes)
-        rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"])
+        rep.ok = (not sweep["failed"] and not (rep.hbm and rep.hbm["errors"]) and not (rep.xcd and not rep.xcd["ok"])
                   and not any(d.get("failed") for _part, d in _part_reports(rep)))
     except Exception as e:                     # a HIP error is a failed device
         log.exception("deep self-test of device %d raised", device)
@@ -302,9 +322,10 @@ def failed_cus(report: DeepReport) -> set[tuple[int, int]]:
 
 def fenceable(report: DeepReport) -> bool:
     """Whether a failed report names CUs that a CU-mask fence could keep tenants off: no HIP
-    error, no HBM errors, no CU whose record is garbled (the `record` kind: then the CU's
-    identity is as doubtful as its result), and at least one failed CU or path."""
-    if report.error or (report.hbm and report.hbm.get("errors")):
+    error, no HBM errors, no failed XCD check (a pair of XCDs is nothing a CU mask can avoid), no CU
+    whose record is garbled (the `record` kind: then the CU's identity is as doubtful as its
+    result), and at least one failed CU or path."""
+    if report.error or (report.hbm and report.hbm.get("errors")) or (report.xcd and not report.xcd.get("ok", True)):
         return False
     if any("record" in f["kinds"] for f in (report.sweep or {}).get("failed", [])):
         return False
@@ -389,6 +410,7 @@ def main(argv: list[str] | None = None) -> int:
                     help="HBM to pattern-check in MiB (default 1024; 0: all free memory less 2 GiB)")
     for part in PARTS:
         ap.add_argument(f"--{part.key}", default="", metavar="all|LIST", help=part.help if part.listed else argparse.SUPPRESS)
+    ap.add_argument("--xcd", default="", metavar="all|LIST", help=argparse.SUPPRESS)   # groups of the XCD check
     ap.add_argument("--fence", type=int, default=0, metavar="N",
                     help="after a failed sweep, print the CU-mask units (at most N) and CUs an agent started with "
                          "--selftest-fence N would fence; changes nothing on the device or the node")
@@ -396,11 +418,12 @@ def main(argv: list[str] | None = None) -> int:
     a = ap.parse_args(argv)
     try:
         select = vars(Selection.parse(**{part.key: getattr(a, part.key) for part in PARTS}))
+        xcd = selftest_xcd.parse_xcd(a.xcd)
     except ValueError as e:
         ap.error(str(e))
     P = probe(required=True)
     nbytes = free_hbm_bytes(P, a.device, a.hbm_mib)
-    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, **select)
+    rep = deep_selftest(P, a.device, hbm_bytes=nbytes, xcd=xcd, **select)
     plan = would_fence(P, a.device, rep, a.fence, **select) if a.fence > 0 and not rep.ok else None
     if a.json:
         print(json.dumps(dict(rep.to_dict(), fence=plan) if a.fence > 0 else rep.to_dict()))
@@ -416,6 +439,10 @@ def main(argv: list[str] | None = None) -> int:
                 bad = d["failed"]
                 print(f"  {part.label} {', '.join(d['checked'])}{part.detail.format(**d)}: "
                       + (", ".join(f"{n} failed on {len(w)} CU(s)" for n, w in sorted(bad.items())) if bad else "all clean"))
+        if rep.xcd:
+            x = rep.xcd
+            print(f"  XCD check {', '.join(x['checked'])}: {x['pairs_verified']} ordered pair(s) of XCDs verified, {x['ms']:.3f} ms: "
+                  + ("all clean" if x["ok"] else ", ".join(f"{g} {'+'.join(k)}" for g, k in x["kinds"].items())))
         if h:
             print(f"  HBM {h['bytes']} B x 2 passes: {h['errors']} errors, fill {h['fill_gbs']:.0f} GB/s, "
                   f"verify {h['verify_gbs']:.0f} GB/s, {h.get('verify_launches', 1)} launch(es) a pass")

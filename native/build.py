@@ -147,6 +147,8 @@ SELFTEST_HOST_TARGETS = {   # target -> (program's stem, its main, the headers i
                ["selftest_host.h", "selftest_paths_host.h", "selftest_scalar_host.h"]),
     "mem": ("nanogpu-selftest-mem-host", "selftest_mem_host_main.cpp",
             ["selftest_host.h", "selftest_paths_host.h", "selftest_mem_host.h"]),
+    "xcd": ("nanogpu-selftest-xcd-host", "selftest_xcd_host_main.cpp",
+            ["selftest_host.h", "selftest_paths_host.h", "selftest_xcd_host.h"]),
 }
 # --selftest-host's values: "plain" and "asan" for target "host", "<target>-plain" and "<target>-asan" for the others
 SELFTEST_HOST_CHOICES = [kind if target == "host" else f"{target}-{kind}"
@@ -202,7 +204,7 @@ def main() -> None:
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
     ap.add_argument("--selftest-host", choices=SELFTEST_HOST_CHOICES,
                     help="build the stand-alone check of the deep self-test's host arithmetic "
-                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups')")
+                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups', xcd-*: the XCD check's)")
     a = ap.parse_args()
     if a.stress:
         print(build_stress(a.stress, force=a.force))

@@ -21,6 +21,9 @@
 //                   and the SGPR file (`cu_sweep_scalar`).
 //   * cu_mem_kernel — and the CU's memory pipeline (`cu_sweep_mem`): global and buffer loads and
 //                   stores, the L1, LDS instruction forms, the transposed read, LDS-DMA, atomics.
+//   * xcd_write / read / ticket / atomic_kernel — a check of the device, not of a CU (`xcd_check`): what one
+//                   XCD wrote, read on another, across a kernel boundary, by release, ticket and acquire
+//                   inside one kernel, and by memory-side atomics from every XCD onto the same words.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
@@ -45,6 +48,7 @@
 #include "nanogpu/selftest_paths_host.h"
 #include "nanogpu/selftest_scalar_host.h"
 #include "nanogpu/selftest_valu_host.h"
+#include "nanogpu/selftest_xcd_host.h"
 
 namespace py = pybind11;
 
@@ -70,6 +74,7 @@ namespace st = nanogpu::selftest;
 #include "probe_scalar.inc"         // cu_sweep_scalar
 #include "probe_mem.inc"            // cu_sweep_mem
 #include "probe_hbm.inc"            // hbm_fill, hbm_verify, hbm_pattern_check
+#include "probe_xcd.inc"            // xcd_check: what one XCD wrote, read on another
 #include "probe_matrix_tile.inc"    // matrix_tile: one instruction of a matrix path on the caller's codes
 
 }  // namespace
@@ -330,6 +335,31 @@ PYBIND11_MODULE(_probe, m) {
       [](const std::string& group) { return mem_lanes(MemPart::names.index(group)); },
       py::arg("group"), py::call_guard<py::gil_scoped_release>(),
       "One workgroup of four waves runs memory group `group`: every lane's raw result words [wave][k][lane].");
+  m.def("xcd_check", &xcd_check, py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
+        py::arg("seed") = 0x5eed5eedu, py::arg("groups") = std::vector<std::string>{"handoff", "ticket", "atomic"},
+        py::arg("inject") = py::none(), py::arg("corrupt") = py::none(),
+        "Check of the device on cu_sweep's grid and stream (rounds 1..4 x CUs workgroups, N of them): data one XCD wrote, read on "
+        "another. Groups: 'handoff' (a write kernel fills 16 KiB a workgroup with plain stores and enters it in its XCD's list; the "
+        "next launch verifies from every XCD one slice of every XCD), 'ticket' (workgroups 8g..8g+7: plain stores, agent-scope "
+        "release, one ticket; the last arriver acquires and verifies the others' 4 KiB slices, which it had read before) and "
+        "'atomic' (adds, or, xor, min, max and a counter from every workgroup onto the same words). No kernel waits for another "
+        "workgroup. records[b] = (write, read, ticket, atomic) sections of workgroup b of each kernel, None where the kernel did not "
+        "run: write (xcc, hw_id, kinds, list position); read (xcc, hw_id, kinds, writer XCDs verified, writer XCDs failed, reader "
+        "ordinal, then the first failure: writer block, its xcc, its hw_id, word, expected, observed, each None without one); ticket "
+        "(xcc, hw_id, kinds, last arriver, ticket, slices verified, writer XCDs verified, failed, the first failure, fold of the words "
+        "read before the ticket); atomic (xcc, hw_id, kinds, duplicates). kinds: bit 0 data, 1 dir (an index read from memory was out "
+        "of range: never used as an address), 2 writer, 3 preread, 4 dup. atomic_words / atomic_expected are the 168 final words and "
+        "the host's, atomic_bad the indices that differ; pairs[group] the ordered (writer xcc, reader xcc) verified; bytes the device "
+        "memory held; ms_kernels and ms the time per kernel and of the sequence; num_regs per kernel and the largest scratch_bytes. "
+        "Test hooks: inject = ('handoff', writer xcc, reader xcc) | ('ticket', group) flips bit 0 of the value word 0 is compared with "
+        "(of that XCD's slices on that XCD's readers; of the first partner's slice on that group's last arriver), ('atomic', word) "
+        "flips bit 0 of the host's expected word; corrupt = (block, byte offset, xor byte): the host XORs one byte of that block's "
+        "hand-off slice between the write and the read kernel, the one synchronisation inside a run.");
+  m.def("xcd_sensitivity", &xcd_sensitivity, py::arg("device"), py::arg("flips"), py::arg("cu_mask") = std::vector<uint32_t>{},
+        py::arg("rounds") = 1, py::arg("seed") = 0x5eed5eedu,
+        "Test hook: for every (word, xor) of `flips` one hand-off on one session with that word of block 0's slice XORed between the "
+        "write and the read kernel. words[i] = (AND, OR) over that run's read sections of (kinds, writer XCDs failed, first bad "
+        "block or -1, its word or -1); records = workgroups per run, seconds = the loop's wall time.");
   m.def(
       "mem_info",
       [](int dev) {
