@@ -13,6 +13,7 @@ and serves the kubelet device plugin (plugin.py) for `nano-gpu/gpu-percent`.
 from __future__ import annotations
 
 import asyncio
+import functools
 import json
 import logging
 import os
@@ -71,23 +72,72 @@ def calibrate(topo: NodeTopology, device: int = 0, host: dict | None = None, bus
     return out
 
 
+# Elements of the basic tile that hold a chosen value instead of the hashed one: between them they
+# set and clear every bit of the bf16 code. 1.0 = 0x3F80 and 2.0 = 0x4000 differ in all eight
+# exponent bits, 255 = 0x437F sets the seven mantissa bits, 129 and 131 are odd and >= 129, and
+# 256 = 0x4380 is the largest magnitude. A's are on (row, k) = (i, i), B's on (k, col) = (8 + i, i),
+# so that no accumulator multiplies two large values.
+_BASIC_TILE_A = {(0, 0): 1, (1, 1): 2, (2, 2): 255, (3, 3): -129, (4, 4): 256, (5, 5): -1}
+_BASIC_TILE_B = {(8, 0): 1, (9, 1): 2, (10, 2): -255, (11, 3): 131, (12, 4): -256, (13, 5): -2}
+
+
+def basic_tile_operands() -> tuple[list[float], list[float]]:
+    """Operands of `gpu_selftest`'s one tile: A[32][16] and B[16][32], row-major, a fixed function
+    of the index. With t = mix32(i) >> 28, element i of the 1,024 is t - 8 where t < 8 and t - 7
+    otherwise, so one of +-1..8 (A's element (r, k) is i = 16 r + k, B's (k, c) is
+    i = 512 + 32 k + c), but for the twelve of _BASIC_TILE_A and _BASIC_TILE_B.
+    tests/test_basic_selftest.py checks each of these conditions:
+
+    * Exact. Every element is an integer of magnitude <= 256, so a bf16 value, and for every
+      accumulator sum_k |a||b| < 2^24 (it is below 2^13), so the fp32 result is exact in any
+      summation order. Below 2^17 every multiple of 2^-7 is an fp32 value too, so one flipped
+      mantissa bit of an operand (2^-7 at the least, times an integer) is not rounded away.
+    * Every element matters. No element is 0: each A[r][k] meets a non-zero B[k][c] and each
+      B[k][c] a non-zero A[r][k], and a flipped sign bit changes the value.
+    * Routing. The rows of A are pairwise distinct, and so are the columns of B. A and B have
+      rank 16, so the 16 k-slices differ, a permutation of k applied to one operand alone changes
+      C, and distinct rows or columns stay distinct in C. A.B differs from what A or B read
+      column-major gives.
+    * Bits. Across A, and across B, each of the 16 bits of the bf16 code is 0 in some element and
+      1 in some element; both signs occur.
+    * C is not constant, and no row or column of C repeats."""
+    a, b, _c = _basic_tile()
+    return list(a), list(b)
+
+
+@functools.lru_cache(maxsize=1)
+def _basic_tile() -> tuple[tuple[float, ...], tuple[float, ...], tuple[float, ...]]:
+    """(A, B, the host's A.B) of `basic_tile_operands`, made once."""
+    from ..probe.selftest_common import mix32
+
+    def hashed(i: int) -> int:
+        t = mix32(i) >> 28
+        return t - 8 if t < 8 else t - 7
+
+    a = [float(_BASIC_TILE_A.get((r, k), hashed(16 * r + k))) for r in range(32) for k in range(16)]
+    b = [float(_BASIC_TILE_B.get((k, c), hashed(512 + 32 * k + c))) for k in range(16) for c in range(32)]
+    c = [sum(a[r * 16 + k] * b[k * 32 + col] for k in range(16)) for r in range(32) for col in range(32)]
+    return tuple(a), tuple(b), tuple(c)
+
+
 def gpu_selftest(P, device: int) -> bool:
     """Active check of one HIP device with the probe's kernels: a bit-exact 16 MiB HBM copy
-    and one bf16 MFMA tile (32x32x16, small integers, so the fp32 result is exact) against
-    a host reference. A device that loads its driver and shows in sysfs can still compute
-    wrong or fault; the agent then reports it Unhealthy (kubelet) and unschedulable (the
-    extender). Runs on the calling thread (HIP's current device)."""
+    and one bf16 MFMA tile (32x32x16, `basic_tile_operands`: integers, so the fp32 result is
+    exact, chosen so that a misrouted row, column or k, a changed element and a flipped bit of
+    an operand code all change it) against a host reference. A device that loads its driver and
+    shows in sysfs can still compute wrong or fault; the agent then reports it Unhealthy
+    (kubelet) and unschedulable (the extender). Runs on the calling thread (HIP's current device)."""
     try:
         if not P.copy_check(device, 1 << 22):
             return False
-        a = [float((i * 7) % 7 - 3) for i in range(32 * 16)]
-        b = [float((i * 5) % 5 - 2) for i in range(16 * 32)]
+        a, b = basic_tile_operands()
         c = P.gemm_tile(a, b)                  # on `device`: copy_check made it current
-        for r in range(32):
-            row = a[r * 16:(r + 1) * 16]
-            for col in range(32):
-                if c[r * 32 + col] != sum(row[k] * b[k * 32 + col] for k in range(16)):
-                    return False
+        want = _basic_tile()[2]
+        if len(c) != len(want):
+            return False
+        for i in range(len(want)):
+            if c[i] != want[i]:
+                return False
         return True
     except Exception:                          # a HIP error is a failed device
         log.exception("self-test of device %d raised", device)

@@ -97,7 +97,40 @@ PYBIND11_MODULE(_probe, m) {
         py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("blocks") = 2048, py::arg("iters") = 2048,
         "bf16 MFMA TFLOP/s on a CU-masked stream.");
   m.def("gemm_tile", &gemm_tile, py::arg("a"), py::arg("b"),
-        "C[32x32] = bf16(A[32x16]) @ bf16(B[16x32]) with one v_mfma_f32_32x32x16_bf16 (fp32 accumulate).");
+        "C[32x32] = bf16(A[32x16]) @ bf16(B[16x32]) with one v_mfma_f32_32x32x16_bf16 (fp32 accumulate). The operands "
+        "are lists of float32: a Python float that is no float32 value is rounded twice, double -> float32 -> bf16 "
+        "(bf16_bits rounds the same way).");
+  m.def(
+      "bf16_bits",
+      [](const py::object& x) {
+        std::vector<uint16_t> out;
+        if (py::isinstance<py::buffer>(x)) {   // float32 words as they lie in memory: no Python float in between
+          const py::buffer_info info = x.cast<py::buffer>().request();
+          if (info.itemsize != 4 || info.format != py::format_descriptor<float>::format() || info.ndim != 1 ||
+              info.strides[0] != 4)
+            throw std::invalid_argument("bf16_bits: a buffer must be one contiguous dimension of float32");
+          out.resize(static_cast<size_t>(info.shape[0]));
+          const char* p = static_cast<const char*>(info.ptr);
+          for (size_t i = 0; i < out.size(); ++i) {
+            float f;
+            std::memcpy(&f, p + 4 * i, 4);
+            out[i] = st::f32_to_bf16_bits(f);
+          }
+        } else {
+          const std::vector<float> v = x.cast<std::vector<float>>();
+          out.resize(v.size());
+          for (size_t i = 0; i < v.size(); ++i) out[i] = st::f32_to_bf16_bits(v[i]);
+        }
+        return out;
+      },
+      py::arg("x"),
+      "The bf16 codes gemm_tile gives its operands: float32 -> bf16, round to nearest even, NaN to a NaN of its sign. "
+      "No GPU involved. x is a list of floats, or a one-dimensional contiguous float32 buffer (a numpy array), whose "
+      "words are read as they are. In a list, a Python float that is no float32 value is rounded twice, double -> "
+      "float32 -> bf16, and the conversion makes a signalling NaN quiet; pass a buffer for exact bit patterns.");
+  m.def("mfma_burn_sums", &mfma_burn_sums, py::arg("device") = 0, py::arg("blocks") = 2, py::arg("iters") = 8,
+        "Test hook: one launch of mfma_throughput's kernel in its checking form, which stores every thread's sum of its "
+        "64 accumulators; [block][thread], 256 threads a block. blocks in 1..8 and iters in 1..1024, else ValueError.");
   m.def(
       "copy_check",
       [](int dev, size_t n_floats, size_t guard_bytes) -> py::object {

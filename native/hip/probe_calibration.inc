@@ -59,7 +59,10 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // MFMA-bound burn: 4 independent 32x32x16 bf16 accumulator chains per wave hide the
-// dependent-accumulator latency; each MFMA is 2*32*32*16 = 32768 FLOP.
+// dependent-accumulator latency; each MFMA is 2*32*32*16 = 32768 FLOP. kStoreSums = false is the
+// timed kernel, which never stores on a healthy device; true stores every thread's sum, so that a
+// test can check the arithmetic burn_tflops charges for (mfma_burn_sums).
+template <bool kStoreSums>
 __global__ __launch_bounds__(256) void mfma_burn(float* out, int iters) {
   const int lane = threadIdx.x & 63;
   bf16x8 a, b;
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(256) void mfma_burn(float* out, int iters) {
   }
   float s = 0.f;
   for (int r = 0; r < 16; ++r) s += c0[r] + c1[r] + c2[r] + c3[r];
-  if (s == 12345.678f) out[blockIdx.x * blockDim.x + threadIdx.x] = s;  // keeps the chains live
+  if (kStoreSums || s == 12345.678f) out[blockIdx.x * blockDim.x + threadIdx.x] = s;  // keeps the chains live
 }
 
 // One wave computes C[32x32] = A[32x16] * B[16x32] with a single bf16 MFMA: the numerics
@@ -97,14 +100,6 @@ __global__ __launch_bounds__(64) void mfma_tile(const __bf16* __restrict__ A, co
 }
 
 // ---------------------------------------------------------------------------- host helpers
-
-uint16_t f32_to_bf16_bits(float f) {  // round to nearest even
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return static_cast<uint16_t>(u >> 16);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
 
 template <class T>
 struct DevBuf {
@@ -128,8 +123,8 @@ double copy_gbs(size_t n, int iters, double ms) {
 std::vector<float> gemm_tile(const std::vector<float>& a, const std::vector<float>& b) {
   if (a.size() != 32 * 16 || b.size() != 16 * 32) throw std::invalid_argument("gemm_tile: A is 32x16, B is 16x32");
   std::vector<uint16_t> ha(a.size()), hb(b.size());
-  for (size_t i = 0; i < a.size(); ++i) ha[i] = f32_to_bf16_bits(a[i]);
-  for (size_t i = 0; i < b.size(); ++i) hb[i] = f32_to_bf16_bits(b[i]);
+  for (size_t i = 0; i < a.size(); ++i) ha[i] = st::f32_to_bf16_bits(a[i]);
+  for (size_t i = 0; i < b.size(); ++i) hb[i] = st::f32_to_bf16_bits(b[i]);
   DevBuf<uint16_t> da(ha.size()), db(hb.size());
   DevBuf<float> dc(32 * 32);
   HIP_OK(hipMemcpy(da.p, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
@@ -296,10 +291,10 @@ double mfma_ms(int dev, const std::vector<uint32_t>& mask, int blocks, int iters
   DevBuf<float> out(static_cast<size_t>(blocks) * 256);
   Stream st(mask);
   Events ev;
-  hipLaunchKernelGGL(mfma_burn, dim3(blocks), dim3(256), 0, st.s, out.p, 8);
+  hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, 8);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev.a, st.s));
-  hipLaunchKernelGGL(mfma_burn, dim3(blocks), dim3(256), 0, st.s, out.p, iters);
+  hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, iters);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(ev.b, st.s));
   return ev.ms();
@@ -317,6 +312,22 @@ py::dict mfma_throughput(int dev, const std::vector<uint32_t>& mask, int blocks,
   d["blocks"] = blocks;
   d["iters"] = iters;
   return d;
+}
+
+// One launch of the checking instantiation of mfma_burn: every thread's sum, [block][thread].
+// Small shapes only, so that it cannot serve as a burn.
+std::vector<float> mfma_burn_sums(int dev, int blocks, int iters) {
+  if (blocks < 1 || blocks > 8 || iters < 1 || iters > 1024)
+    throw std::invalid_argument("mfma_burn_sums: blocks in 1..8, iters in 1..1024");
+  HIP_OK(hipSetDevice(dev));
+  const size_t n = static_cast<size_t>(blocks) * 256;
+  DevBuf<float> out(n);
+  HIP_OK(hipMemset(out.p, 0xff, n * sizeof(float)));
+  hipLaunchKernelGGL(mfma_burn<true>, dim3(blocks), dim3(256), 0, 0, out.p, iters);
+  HIP_OK(hipGetLastError());
+  std::vector<float> h(n);
+  HIP_OK(hipMemcpy(h.data(), out.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return h;
 }
 
 // Co-located tenants: one MFMA burn per CU mask, each on its own CU-masked stream, all
@@ -338,13 +349,13 @@ std::vector<double> mfma_colocated(int dev, const std::vector<std::vector<uint32
     streams.emplace_back(new Stream(masks[i]));
     evs.emplace_back(new Events());
     outs.emplace_back(new DevBuf<float>(static_cast<size_t>(blocks[i]) * 256));
-    hipLaunchKernelGGL(mfma_burn, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, 8);  // warm-up
+    hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, 8);  // warm-up
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipDeviceSynchronize());
   for (size_t i = 0; i < n; ++i) {
     HIP_OK(hipEventRecord(evs[i]->a, streams[i]->s));
-    hipLaunchKernelGGL(mfma_burn, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, iters);
+    hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, iters);
     HIP_OK(hipEventRecord(evs[i]->b, streams[i]->s));
   }
   HIP_OK(hipGetLastError());
@@ -415,11 +426,11 @@ std::vector<double> mixed_colocated(int dev, const std::vector<uint32_t>& hbm_ma
   DevBuf<float> out(static_cast<size_t>(mfma_blocks) * 256);
   HIP_OK(hipMemset(src.p, 0, n * sizeof(float4)));
   hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, sc.s, src.p, dst.p, n);    // warm-up
-  hipLaunchKernelGGL(mfma_burn, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, 8);
+  hipLaunchKernelGGL(mfma_burn<false>, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, 8);
   HIP_OK(hipGetLastError());
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipEventRecord(em.a, sm.s));
-  hipLaunchKernelGGL(mfma_burn, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, mfma_iters);
+  hipLaunchKernelGGL(mfma_burn<false>, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, mfma_iters);
   HIP_OK(hipEventRecord(em.b, sm.s));
   HIP_OK(hipEventRecord(ec.a, sc.s));
   for (int it = 0; it < iters; ++it)

@@ -1,11 +1,12 @@
 // Host/device-shared arithmetic of the deep self-test (native/hip/probe_sweep.inc: cu_sweep; probe_hbm.inc:
-// hbm_fill, hbm_verify). Plain C++ with no HIP dependency, so the host side can be built
+// hbm_fill, hbm_verify) and the bf16 rounding of the basic one's tile (gemm_tile). Plain C++ with no HIP dependency, so the host side can be built
 // and run under sanitizers on its own (native/tests/selftest_host_main.cpp). The Python
 // twin of the pattern is nanogpu/probe/selftest.py.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -84,6 +85,19 @@ inline void sweep_expected(int32_t out[32 * 32]) {
         for (int k = 0; k < 16; ++k) acc += sweep_a(s, r, k) * sweep_b(s, k, c);
       out[r * 32 + c] = acc;
     }
+}
+
+// ---- bf16 operands of the one-tile check -------------------------------------------------
+// The bf16 code of a float, round to nearest even (gemm_tile's operands). A finite value beyond
+// the largest bf16 rounds to Inf, Inf stays Inf, and a NaN stays a NaN of its sign: its high half
+// with the quiet bit set, since the payload may lie in the low half alone (0x7f800001).
+inline uint16_t f32_to_bf16_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x0040u);
+  if ((u & 0x7f800000u) == 0x7f800000u) return static_cast<uint16_t>(u >> 16);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return static_cast<uint16_t>(u >> 16);
 }
 
 // ---- sweep record -----------------------------------------------------------------------

@@ -2,8 +2,11 @@
 // no GPU code involved: build it with `python native/build.py --selftest-host asan` to run it
 // under ASan + UBSan. The pinned pattern values are the ones tests/test_selftest_deep.py pins
 // for the Python twin, so the kernels' header and the twin cannot drift apart unnoticed.
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "nanogpu/selftest_host.h"
@@ -20,7 +23,76 @@ static int failures = 0;
     }                                                                  \
   } while (0)
 
+static float word_float(uint32_t u) {
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+static bool code_is_nan(uint16_t c) { return (c & 0x7f80u) == 0x7f80u && (c & 0x007fu) != 0; }
+
+// f32_to_bf16_bits written another way: the two bf16 values on either side of f, by truncation, and the
+// nearer of them in double arithmetic (the differences of two floats are exact there); a tie goes to
+// the even code. The code above the largest finite one is Inf's, 2^128 by its exponent field, so an
+// overflowing value rounds to Inf when it is at least half-way there. `f` is no NaN.
+static uint16_t bf16_by_distance(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  const uint16_t lo = static_cast<uint16_t>(u >> 16);   // toward zero
+  if ((u & 0xffffu) == 0 || (lo & 0x7fffu) == 0x7f80u) return lo;
+  const uint16_t hi = static_cast<uint16_t>(lo + 1);    // away from zero: the magnitude is the code's low 15 bits
+  const auto value = [](uint16_t c) {
+    const int e = (c >> 7) & 0xff, m = c & 0x7f;
+    const double mag = e == 0 ? std::ldexp(static_cast<double>(m), -133) : std::ldexp(static_cast<double>(128 + m), e - 134);
+    return (c & 0x8000u) ? -mag : mag;
+  };
+  const double x = static_cast<double>(f), dlo = std::fabs(x - value(lo)), dhi = std::fabs(value(hi) - x);
+  if (dlo < dhi) return lo;
+  if (dhi < dlo) return hi;
+  return (lo & 1u) ? hi : lo;
+}
+
 int main() {
+  // bf16 rounding: every high half with the low halves that decide a rounding
+  {
+    const uint32_t lows[] = {0x0000u, 0x0001u, 0x7fffu, 0x8000u, 0x8001u, 0xffffu};
+    long cases = 0, nans = 0, ties_up = 0, ties_down = 0, to_inf = 0, carries = 0, bad = 0;
+    for (uint32_t high = 0; high < 0x10000u; ++high)
+      for (uint32_t low : lows) {
+        const uint32_t u = (high << 16) | low;
+        const uint16_t got = st::f32_to_bf16_bits(word_float(u));
+        ++cases;
+        if ((u & 0x7fffffffu) > 0x7f800000u) {   // NaN in: NaN out, same sign
+          ++nans;
+          if (!(code_is_nan(got) && (got >> 15) == (u >> 31))) ++bad;
+          continue;
+        }
+        const uint16_t want = bf16_by_distance(word_float(u));
+        if (got != want) ++bad;
+        if (low == 0x8000u) ++(want == high ? ties_down : ties_up);
+        if ((want & 0x7fffu) == 0x7f80u && (high & 0x7fffu) != 0x7f80u) ++to_inf;
+        if ((want & 0x7fu) == 0 && (high & 0x7fu) == 0x7fu) ++carries;
+      }
+    CHECK(bad == 0);
+    CHECK(cases == 393216);
+    CHECK(nans == 2 * (127 * 6 + 5));   // high halves 0x7f81..0x7fff with any low half, 0x7f80 with a non-zero one
+    CHECK(ties_up == ties_down && ties_up > 0);
+    CHECK(to_inf == 2 * 3);             // 0x7f7f with the low halves 0x8000 and above rounds to Inf, either sign
+    CHECK(carries > 0);
+    CHECK(st::f32_to_bf16_bits(word_float(0x7f800001u)) == 0x7fc0u);   // payload in the low half alone
+    CHECK(st::f32_to_bf16_bits(word_float(0xff800001u)) == 0xffc0u);
+    CHECK(st::f32_to_bf16_bits(word_float(0x7f7fffffu)) == 0x7f80u);   // the largest float -> Inf
+    CHECK(st::f32_to_bf16_bits(word_float(0x7f7f7fffu)) == 0x7f7fu);   // below half-way: the largest bf16
+    CHECK(st::f32_to_bf16_bits(word_float(0x7f800000u)) == 0x7f80u && st::f32_to_bf16_bits(word_float(0xff800000u)) == 0xff80u);
+    CHECK(st::f32_to_bf16_bits(word_float(0x00000000u)) == 0x0000u && st::f32_to_bf16_bits(word_float(0x80000000u)) == 0x8000u);
+    CHECK(st::f32_to_bf16_bits(word_float(0x3f808000u)) == 0x3f80u);   // tie, even neighbour below
+    CHECK(st::f32_to_bf16_bits(word_float(0x3f818000u)) == 0x3f82u);   // tie, even neighbour above
+    CHECK(st::f32_to_bf16_bits(word_float(0x3fffffffu)) == 0x4000u);   // carry from the mantissa into the exponent
+    CHECK(st::f32_to_bf16_bits(word_float(0x00008000u)) == 0x0000u);   // subnormal tie to +0
+    CHECK(st::f32_to_bf16_bits(word_float(0x00008001u)) == 0x0001u);   // the smallest bf16 subnormal
+    CHECK(st::f32_to_bf16_bits(word_float(0x007fffffu)) == 0x0080u);   // the largest subnormal float -> the smallest normal
+  }
+
   // pattern
   CHECK(st::mix32(1) == 0x514e28b7u);
   CHECK(st::mix32(0xdeadbeefu) == 0x0de5c6a9u);
