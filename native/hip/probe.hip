@@ -10,6 +10,7 @@
 //   * mfma_burn   — bf16 MFMA throughput of a masked stream (isolation check: TFLOP/s
 //                   must scale with the CUs granted);
 //   * hbm_copy    — streaming HBM3E bandwidth (16 B/lane, grid >> 256 WGs);
+//                   these two rates, alone or co-located, are lists of Tenant behind one run_tenants;
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
 //   * cu_sweep_kernel, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA
 //                   pipes and LDS (`cu_sweep`), and free HBM against an address-derived pattern.
@@ -67,7 +68,7 @@ namespace st = nanogpu::selftest;
 // is the order of dependency; the matrix_tile runner comes last because kernel templates are
 // instantiated in the order in which host code first names them, and that is the order of the
 // kernels in the code object.
-#include "probe_calibration.inc"    // hbm_copy, cu_census, mfma_burn, mfma_tile; DevBuf, Stream, Events
+#include "probe_calibration.inc"    // hbm_copy, cu_census, mfma_burn, mfma_tile; DevBuf, Stream, Events; Tenant
 #include "probe_selftest_core.inc"  // NameTable, CuSession, PartSession and the part bindings, Sensitivity
 #include "probe_sweep.inc"          // cu_sweep and cu_sweep_paths: the matrix unit and LDS
 #include "probe_valu.inc"           // cu_sweep_valu

@@ -101,13 +101,35 @@ __global__ __launch_bounds__(64) void mfma_tile(const __bf16* __restrict__ A, co
 
 // ---------------------------------------------------------------------------- host helpers
 
+// DevBuf, Stream and Events own HIP handles: they move and never copy, and abandon() gives a handle
+// up without freeing it (peer_bandwidth after a timeout).
+struct OomIsBadAlloc {};
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;
+  DevBuf() = default;
   explicit DevBuf(size_t n) { HIP_OK(hipMalloc(&p, n * sizeof(T))); }
+  // An allocation that does not fit is the caller's to shrink, not a device fault.
+  DevBuf(size_t n, OomIsBadAlloc) {
+    const hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      throw std::bad_alloc();
+    }
+    HIP_OK(e);
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    return *this;
+  }
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
+  void abandon() { p = nullptr; }
 };
 
 // mfma_burn: 4 chains a wave, 4 waves a block, 32768 FLOP an instruction.
@@ -145,9 +167,17 @@ struct Stream {
     else
       HIP_OK(hipExtStreamCreateWithCUMask(&s, static_cast<uint32_t>(mask.size()), mask.data()));
   }
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  Stream(Stream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+  Stream& operator=(Stream&& o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
   ~Stream() {
     if (s) (void)hipStreamDestroy(s);
   }
+  void abandon() { s = nullptr; }
 };
 
 struct Events {
@@ -156,10 +186,19 @@ struct Events {
     HIP_OK(hipEventCreate(&a));
     HIP_OK(hipEventCreate(&b));
   }
-  ~Events() {
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
+  Events(const Events&) = delete;
+  Events& operator=(const Events&) = delete;
+  Events(Events&& o) noexcept : a(std::exchange(o.a, nullptr)), b(std::exchange(o.b, nullptr)) {}
+  Events& operator=(Events&& o) noexcept {
+    std::swap(a, o.a);
+    std::swap(b, o.b);
+    return *this;
   }
+  ~Events() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void abandon() { a = b = nullptr; }
   float ms() {
     HIP_OK(hipEventSynchronize(b));
     float t = 0.f;
@@ -249,31 +288,81 @@ CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
   return res;
 }
 
+// One tenant of a device in a rate probe: a stream under its CU mask (empty: every CU) with its own
+// events, and the work it repeats there: `iters` launches of an HBM copy of n float4, or one launch of an
+// MFMA burn of `blocks` blocks that loops `iters` times. The callers have checked the shapes.
+struct Tenant {
+  Stream st;
+  Events ev;
+  int iters;
+  size_t n = 0;   // a copy: n > 0
+  unsigned grid = 0;
+  DevBuf<float4> src, dst;
+  int blocks = 0;   // a burn
+  DevBuf<float> out;
+
+  static Tenant copy(const std::vector<uint32_t>& mask, size_t n, unsigned grid, int iters) {
+    Tenant t{Stream(mask), Events(), iters};
+    t.n = n;
+    t.grid = grid;
+    t.src = DevBuf<float4>(n);
+    t.dst = DevBuf<float4>(n);
+    // on the tenant's own stream, which does not wait for the null stream: ordered before the warm-up
+    HIP_OK(hipMemsetAsync(t.src.p, 0, n * sizeof(float4), t.st.s));
+    return t;
+  }
+  static Tenant burn(const std::vector<uint32_t>& mask, int blocks, int iters) {
+    Tenant t{Stream(mask), Events(), iters};
+    t.blocks = blocks;
+    t.out = DevBuf<float>(static_cast<size_t>(blocks) * 256);
+    return t;
+  }
+  void copy_once() const { hipLaunchKernelGGL(hbm_copy, dim3(grid), dim3(kCopyBlock), 0, st.s, src.p, dst.p, n); }
+  void burn_once(int loops) const {
+    hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, loops);
+  }
+  void warm_up() const { n ? copy_once() : burn_once(8); }
+  void enqueue_timed() const {
+    HIP_OK(hipEventRecord(ev.a, st.s));
+    if (n)
+      for (int i = 0; i < iters; ++i) copy_once();
+    else
+      burn_once(iters);
+    HIP_OK(hipEventRecord(ev.b, st.s));
+  }
+  double rate() { return n ? copy_gbs(n, iters, ev.ms()) : burn_tflops(blocks, iters, ev.ms()); }
+};
+
+// The one procedure behind the rate probes. Every tenant warms up and the device drains; then the timed
+// work of all of them is enqueued back to back, so that they run together, each between its own events.
+// Launch errors are read after the loops: nothing stands between two timed launches.
+std::vector<double> run_tenants(std::vector<Tenant>& tenants) {
+  for (const Tenant& t : tenants) t.warm_up();
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  for (const Tenant& t : tenants) t.enqueue_timed();
+  HIP_OK(hipGetLastError());
+  std::vector<double> rates;
+  for (Tenant& t : tenants) rates.push_back(t.rate());
+  return rates;
+}
+
 double hbm_bandwidth(int dev, size_t bytes, int iters) {
   HIP_OK(hipSetDevice(dev));
   const size_t n = bytes / sizeof(float4);
   if (n == 0 || iters <= 0) throw std::invalid_argument("hbm_bandwidth: bytes/iters must be positive");
-  const dim3 grid(copy_grid(n));
-  DevBuf<float4> a(n), b(n);
-  HIP_OK(hipMemset(a.p, 0, n * sizeof(float4)));
-  Stream st({});
-  Events ev;
-  hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);  // warm-up
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev.a, st.s));
-  for (int i = 0; i < iters; ++i)
-    hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev.b, st.s));
-  return copy_gbs(n, iters, ev.ms());
+  const unsigned grid = copy_grid(n);
+  std::vector<Tenant> tenants;
+  tenants.push_back(Tenant::copy({}, n, grid, iters));
+  return run_tenants(tenants)[0];
 }
 
 py::list census(int dev, const std::vector<uint32_t>& mask, int blocks, int sleep_iters) {
   HIP_OK(hipSetDevice(dev));
   if (blocks <= 0 || blocks > (1 << 20)) throw std::invalid_argument("census: bad block count");
   DevBuf<uint32_t> out(static_cast<size_t>(blocks) * 3);
-  HIP_OK(hipMemset(out.p, 0xff, static_cast<size_t>(blocks) * 3 * sizeof(uint32_t)));
   Stream st(mask);
+  HIP_OK(hipMemsetAsync(out.p, 0xff, static_cast<size_t>(blocks) * 3 * sizeof(uint32_t), st.s));
   hipLaunchKernelGGL(cu_census, dim3(blocks), dim3(64), 0, st.s, out.p, sleep_iters);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(st.s));
@@ -284,31 +373,21 @@ py::list census(int dev, const std::vector<uint32_t>& mask, int blocks, int slee
   return res;
 }
 
-double mfma_ms(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
-  HIP_OK(hipSetDevice(dev));
-  if (blocks <= 0 || iters <= 0) throw std::invalid_argument("mfma_throughput: bad shape");
-  check_burn_blocks(blocks);
-  DevBuf<float> out(static_cast<size_t>(blocks) * 256);
-  Stream st(mask);
-  Events ev;
-  hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, 8);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev.a, st.s));
-  hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, iters);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipEventRecord(ev.b, st.s));
-  return ev.ms();
-}
-
 py::dict mfma_throughput(int dev, const std::vector<uint32_t>& mask, int blocks, int iters) {
-  double ms = 0.0;
+  double ms = 0.0, tflops = 0.0;
   {
     py::gil_scoped_release nogil;  // device work without the GIL; py objects built after
-    ms = mfma_ms(dev, mask, blocks, iters);
+    HIP_OK(hipSetDevice(dev));
+    if (blocks <= 0 || iters <= 0) throw std::invalid_argument("mfma_throughput: bad shape");
+    check_burn_blocks(blocks);
+    std::vector<Tenant> tenants;
+    tenants.push_back(Tenant::burn(mask, blocks, iters));
+    tflops = run_tenants(tenants)[0];
+    ms = tenants[0].ev.ms();
   }
   py::dict d;
   d["ms"] = ms;
-  d["tflops"] = burn_tflops(blocks, iters, ms);
+  d["tflops"] = tflops;
   d["blocks"] = blocks;
   d["iters"] = iters;
   return d;
@@ -340,28 +419,10 @@ std::vector<double> mfma_colocated(int dev, const std::vector<std::vector<uint32
   HIP_OK(hipSetDevice(dev));
   if (masks.empty() || masks.size() != blocks.size() || iters <= 0)
     throw std::invalid_argument("mfma_colocated: one block count per mask, iters > 0");
-  const size_t n = masks.size();
-  std::vector<std::unique_ptr<Stream>> streams;
-  std::vector<std::unique_ptr<Events>> evs;
-  std::vector<std::unique_ptr<DevBuf<float>>> outs;
   for (int b : blocks) check_burn_blocks(b);
-  for (size_t i = 0; i < n; ++i) {
-    streams.emplace_back(new Stream(masks[i]));
-    evs.emplace_back(new Events());
-    outs.emplace_back(new DevBuf<float>(static_cast<size_t>(blocks[i]) * 256));
-    hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, 8);  // warm-up
-  }
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipDeviceSynchronize());
-  for (size_t i = 0; i < n; ++i) {
-    HIP_OK(hipEventRecord(evs[i]->a, streams[i]->s));
-    hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks[i]), dim3(256), 0, streams[i]->s, outs[i]->p, iters);
-    HIP_OK(hipEventRecord(evs[i]->b, streams[i]->s));
-  }
-  HIP_OK(hipGetLastError());
-  std::vector<double> tf(n);
-  for (size_t i = 0; i < n; ++i) tf[i] = burn_tflops(blocks[i], iters, evs[i]->ms());
-  return tf;
+  std::vector<Tenant> tenants;
+  for (size_t i = 0; i < masks.size(); ++i) tenants.push_back(Tenant::burn(masks[i], blocks[i], iters));
+  return run_tenants(tenants);
 }
 
 // Co-located streaming tenants: one HBM copy per CU mask, each on its own CU-masked stream,
@@ -379,31 +440,10 @@ std::vector<double> hbm_colocated(int dev, const std::vector<std::vector<uint32_
   if (iters_each.size() != k) throw std::invalid_argument("hbm_colocated: one iteration count per mask");
   for (int it : iters_each)
     if (it <= 0 || it > 1000) throw std::invalid_argument("hbm_colocated: iterations in 1..1000");
-  std::vector<std::unique_ptr<Stream>> streams;
-  std::vector<std::unique_ptr<Events>> evs;
-  std::vector<std::unique_ptr<DevBuf<float4>>> src, dst;
-  const dim3 grid(copy_grid(n));
-  for (size_t i = 0; i < k; ++i) {
-    streams.emplace_back(new Stream(masks[i]));
-    evs.emplace_back(new Events());
-    src.emplace_back(new DevBuf<float4>(n));
-    dst.emplace_back(new DevBuf<float4>(n));
-    HIP_OK(hipMemset(src[i]->p, 0, n * sizeof(float4)));
-    hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, streams[i]->s, src[i]->p, dst[i]->p, n);  // warm-up
-  }
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipDeviceSynchronize());
-  for (size_t i = 0; i < k; ++i) {
-    HIP_OK(hipEventRecord(evs[i]->a, streams[i]->s));
-    for (int it = 0; it < iters_each[i]; ++it)
-      hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, streams[i]->s, src[i]->p, dst[i]->p, n);
-    HIP_OK(hipEventRecord(evs[i]->b, streams[i]->s));
-  }
-  HIP_OK(hipGetLastError());
-  std::vector<double> gbs(k);
-  for (size_t i = 0; i < k; ++i)
-    gbs[i] = copy_gbs(n, iters_each[i], evs[i]->ms());
-  return gbs;
+  const unsigned grid = copy_grid(n);
+  std::vector<Tenant> tenants;
+  for (size_t i = 0; i < k; ++i) tenants.push_back(Tenant::copy(masks[i], n, grid, iters_each[i]));
+  return run_tenants(tenants);
 }
 
 // A streaming tenant next to a compute-bound one: an HBM copy on `hbm_mask` and an MFMA
@@ -418,27 +458,13 @@ std::vector<double> mixed_colocated(int dev, const std::vector<uint32_t>& hbm_ma
   const size_t n = bytes / sizeof(float4);
   if (n == 0 || iters <= 0 || mfma_blocks <= 0 || mfma_iters <= 0)
     throw std::invalid_argument("mixed_colocated: bytes, iters and the burn shape must be positive");
-  const dim3 grid(copy_grid(n));
+  const unsigned grid = copy_grid(n);
   check_burn_blocks(mfma_blocks);
-  Stream sc(hbm_mask), sm(mfma_mask);
-  Events ec, em;
-  DevBuf<float4> src(n), dst(n);
-  DevBuf<float> out(static_cast<size_t>(mfma_blocks) * 256);
-  HIP_OK(hipMemset(src.p, 0, n * sizeof(float4)));
-  hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, sc.s, src.p, dst.p, n);    // warm-up
-  hipLaunchKernelGGL(mfma_burn<false>, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, 8);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipEventRecord(em.a, sm.s));
-  hipLaunchKernelGGL(mfma_burn<false>, dim3(mfma_blocks), dim3(256), 0, sm.s, out.p, mfma_iters);
-  HIP_OK(hipEventRecord(em.b, sm.s));
-  HIP_OK(hipEventRecord(ec.a, sc.s));
-  for (int it = 0; it < iters; ++it)
-    hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, sc.s, src.p, dst.p, n);
-  HIP_OK(hipEventRecord(ec.b, sc.s));
-  HIP_OK(hipGetLastError());
-  const double gbs = copy_gbs(n, iters, ec.ms());
-  return {gbs, burn_tflops(mfma_blocks, mfma_iters, em.ms())};
+  std::vector<Tenant> tenants;   // the burn first: it is under way when the first timed copy starts
+  tenants.push_back(Tenant::burn(mfma_mask, mfma_blocks, mfma_iters));
+  tenants.push_back(Tenant::copy(hbm_mask, n, grid, iters));
+  const std::vector<double> rates = run_tenants(tenants);
+  return {rates[1], rates[0]};
 }
 
 struct PeerRate {
@@ -499,71 +525,51 @@ PeerRate peer_bandwidth(int src, int dst, size_t bytes, int iters, double deadli
     (void)hipGetLastError();
     r.peer_access = true;
   }
-  // owned until a timeout abandons them
-  hipStream_t ss = nullptr, st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  float4 *a = nullptr, *b = nullptr;
-  bool abandoned = false;
-  auto cleanup = [&] {
-    if (abandoned) return;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (ss) (void)hipStreamDestroy(ss);
-    if (st) (void)hipStreamDestroy(st);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-  };
+  // A transfer that missed the deadline abandons what it holds and never frees it (see PeerTimeout).
+  HIP_OK(hipSetDevice(src));
+  DevBuf<float4> a(n);
+  Stream ss({});
+  HIP_OK(hipMemsetAsync(a.p, 0, n * sizeof(float4), ss.s));
+  hipEvent_t fill = nullptr;
+  HIP_OK(hipEventCreateWithFlags(&fill, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(fill, ss.s));
+  const bool filled = wait_event(fill, deadline);
+  (void)hipEventDestroy(fill);
+  if (!filled) {
+    a.abandon(), ss.abandon();
+    throw PeerTimeout("peer_bandwidth: the source fill on GPU " + std::to_string(src) + " did not finish");
+  }
+  HIP_OK(hipSetDevice(dst));
+  DevBuf<float4> b(n);
+  Stream st({});
+  Events ev;
   auto timed = [&](const char* what, auto&& enqueue) -> double {   // seconds of `enqueue`'s work
-    HIP_OK(hipEventRecord(e0, st));
+    HIP_OK(hipEventRecord(ev.a, st.s));
     enqueue();
-    HIP_OK(hipEventRecord(e1, st));
-    if (!wait_event(e1, deadline)) {
-      abandoned = true;
+    HIP_OK(hipEventRecord(ev.b, st.s));
+    if (!wait_event(ev.b, deadline)) {
+      a.abandon(), b.abandon(), ss.abandon(), st.abandon(), ev.abandon();
       throw PeerTimeout(std::string("peer_bandwidth ") + std::to_string(src) + "->" + std::to_string(dst) + ": " +
                         what + " did not finish within " + std::to_string(deadline_s) + " s");
     }
     float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_OK(hipEventElapsedTime(&ms, ev.a, ev.b));
     return ms * 1e-3;
   };
-  try {
-    HIP_OK(hipSetDevice(src));
-    HIP_OK(hipMalloc(&a, n * sizeof(float4)));
-    HIP_OK(hipStreamCreateWithFlags(&ss, hipStreamNonBlocking));
-    HIP_OK(hipMemsetAsync(a, 0, n * sizeof(float4), ss));
-    hipEvent_t fill = nullptr;
-    HIP_OK(hipEventCreateWithFlags(&fill, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(fill, ss));
-    const bool filled = wait_event(fill, deadline);
-    (void)hipEventDestroy(fill);
-    if (!filled) {
-      abandoned = true;
-      throw PeerTimeout("peer_bandwidth: the source fill on GPU " + std::to_string(src) + " did not finish");
-    }
-    HIP_OK(hipSetDevice(dst));
-    HIP_OK(hipMalloc(&b, n * sizeof(float4)));
-    HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIP_OK(hipEventCreate(&e0));
-    HIP_OK(hipEventCreate(&e1));
-    const double nb = static_cast<double>(n * sizeof(float4));
-    timed("SDMA warm-up", [&] { HIP_OK(hipMemcpyPeerAsync(b, dst, a, src, n * sizeof(float4), st)); });
-    r.dma_gbs = nb * iters / timed("SDMA copies", [&] {
-      for (int i = 0; i < iters; ++i) HIP_OK(hipMemcpyPeerAsync(b, dst, a, src, n * sizeof(float4), st));
+  const double nb = static_cast<double>(n * sizeof(float4));
+  timed("SDMA warm-up", [&] { HIP_OK(hipMemcpyPeerAsync(b.p, dst, a.p, src, n * sizeof(float4), st.s)); });
+  r.dma_gbs = nb * iters / timed("SDMA copies", [&] {
+    for (int i = 0; i < iters; ++i) HIP_OK(hipMemcpyPeerAsync(b.p, dst, a.p, src, n * sizeof(float4), st.s));
+  }) / 1e9;
+  if (r.peer_access) {
+    timed("pull warm-up", [&] {
+      hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);
+      HIP_OK(hipGetLastError());
+    });
+    r.pull_gbs = nb * iters / timed("pull copies", [&] {
+      for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st.s, a.p, b.p, n);
+      HIP_OK(hipGetLastError());
     }) / 1e9;
-    if (r.peer_access) {
-      timed("pull warm-up", [&] {
-        hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st, a, b, n);
-        HIP_OK(hipGetLastError());
-      });
-      r.pull_gbs = nb * iters / timed("pull copies", [&] {
-        for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(hbm_copy, grid, dim3(kCopyBlock), 0, st, a, b, n);
-        HIP_OK(hipGetLastError());
-      }) / 1e9;
-    }
-  } catch (...) {
-    cleanup();
-    throw;
   }
-  cleanup();
   return r;
 }

@@ -104,20 +104,7 @@ PatternResult hbm_pattern_check(int dev, size_t bytes, uint32_t seed, int passes
   const auto verify_spans = st::launch_spans(n, launch_blocks_arg(verify_launch_blocks));
   const uint32_t vseed = verify_seed < 0 ? seed : static_cast<uint32_t>(verify_seed);
 
-  struct Buf {   // an allocation that does not fit is the caller's to shrink, not a device fault
-    unsigned char* p = nullptr;
-    explicit Buf(size_t b) {
-      const hipError_t e = hipMalloc(&p, b);
-      if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        throw std::bad_alloc();
-      }
-      HIP_OK(e);
-    }
-    ~Buf() {
-      if (p) (void)hipFree(p);
-    }
-  } whole(bytes + 2 * guard_bytes);
+  DevBuf<unsigned char> whole(bytes + 2 * guard_bytes, OomIsBadAlloc{});
   u32x4* const data = reinterpret_cast<u32x4*>(whole.p + guard_bytes);
   if (guard_bytes) {
     HIP_OK(hipMemset(whole.p, kGuardByte, guard_bytes));
