@@ -41,7 +41,9 @@ format, joined with what it granted:
 A pod's utilisation is its share of its device's busy time: the container's CUs over the
 device's CUs, times `nanogpu_device_busy_percent` (spatial sharing gives each tenant its own
 CUs, which the co-location measurements in profiles/gpu_calibration.md confirm). A sysfs file
-that this GPU or partition does not have is left out rather than reported as zero.
+that this GPU or partition does not have is left out rather than reported as zero, with one
+exception: on some hosts amdgpu shows mem_info_vram_total without mem_info_vram_used, and then
+the used bytes are the HIP runtime's (the probe's `mem_info`: total minus free).
 """
 from __future__ import annotations
 
@@ -63,6 +65,22 @@ def _read_int(p: Path) -> int | None:
         return int(p.read_text().strip())
     except (OSError, ValueError):
         return None
+
+
+def _runtime_vram_used(device: int) -> int | None:
+    """The HIP runtime's total minus what it can still allocate on `device`, for an amdgpu that
+    shows mem_info_vram_total and no mem_info_vram_used. None where the probe is
+    not built or the runtime has no such device."""
+    from ..native import probe
+
+    P = probe()
+    if P is None:
+        return None
+    try:
+        free, total = P.mem_info(device)
+    except RuntimeError:
+        return None
+    return total - free
 
 
 def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root: str = "",
@@ -103,6 +121,8 @@ def render(topo, plugin=None, render_minors: list[int] | None = None, sysfs_root
         for rows, f in ((busy, "gpu_busy_percent"), (mbusy, "mem_busy_percent"),
                         (used, "mem_info_vram_used"), (total, "mem_info_vram_total")):
             v = _read_int(base / f)
+            if v is None and rows is used and not sysfs_root and (base / "mem_info_vram_total").exists():
+                v = _runtime_vram_used(i)   # the live device only: a fixture tree is not this machine
             if v is not None:
                 rows.append((_labels(device=i), v))
     gpus = {g.index: g for g in topo.gpus}

@@ -53,11 +53,15 @@
 
 namespace py = pybind11;
 
+// A failed call is reported here, once: the runtime also keeps it as its last error, which the
+// check after some later, sound launch would report again as that launch's.
 #define HIP_OK(expr)                                                                    \
   do {                                                                                  \
     hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
+    if (e_ != hipSuccess) {                                                             \
+      (void)hipGetLastError();                                                          \
       throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));      \
+    }                                                                                   \
   } while (0)
 
 namespace {
@@ -371,7 +375,7 @@ PYBIND11_MODULE(_probe, m) {
       "One workgroup of four waves runs memory group `group`: every lane's raw result words [wave][k][lane].");
   m.def("xcd_check", &xcd_check, py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{}, py::arg("rounds") = 4,
         py::arg("seed") = 0x5eed5eedu, py::arg("groups") = std::vector<std::string>{"handoff", "ticket", "atomic"},
-        py::arg("inject") = py::none(), py::arg("corrupt") = py::none(),
+        py::arg("inject") = py::none(), py::arg("corrupt") = py::none(), py::arg("blocks") = 0,
         "Check of the device on cu_sweep's grid and stream (rounds 1..4 x CUs workgroups, N of them): data one XCD wrote, read on "
         "another. Groups: 'handoff' (a write kernel fills 16 KiB a workgroup with plain stores and enters it in its XCD's list; the "
         "next launch verifies from every XCD one slice of every XCD), 'ticket' (workgroups 8g..8g+7: plain stores, agent-scope "
@@ -388,7 +392,8 @@ PYBIND11_MODULE(_probe, m) {
         "Test hooks: inject = ('handoff', writer xcc, reader xcc) | ('ticket', group) flips bit 0 of the value word 0 is compared with "
         "(of that XCD's slices on that XCD's readers; of the first partner's slice on that group's last arriver), ('atomic', word) "
         "flips bit 0 of the host's expected word; corrupt = (block, byte offset, xor byte): the host XORs one byte of that block's "
-        "hand-off slice between the write and the read kernel, the one synchronisation inside a run.");
+        "hand-off slice between the write and the read kernel, the one synchronisation inside a run; blocks > 0: N is that many "
+        "workgroups (1..1024) whatever rounds x CUs gives, for grids no whole CU-mask unit has, such as one ticket group of three.");
   m.def("xcd_sensitivity", &xcd_sensitivity, py::arg("device"), py::arg("flips"), py::arg("cu_mask") = std::vector<uint32_t>{},
         py::arg("rounds") = 1, py::arg("seed") = 0x5eed5eedu,
         "Test hook: for every (word, xor) of `flips` one hand-off on one session with that word of block 0's slice XORed between the "

@@ -78,9 +78,10 @@ struct CuRun {
 // cu_sweep_scalar and cu_sweep_mem).
 class CuSession {
  protected:
-  CuSession(const char* who, int dev, const std::vector<uint32_t>& mask, int rounds, int record_words)
-      : who_(who), stream_(mask), blocks_(grid(who_, dev, mask, rounds)), record_words_(record_words),
-        out_(static_cast<size_t>(blocks_) * record_words) {}
+  // `blocks` > 0 (test hook): that many workgroups, whatever rounds x (enabled CUs) gives.
+  CuSession(const char* who, int dev, const std::vector<uint32_t>& mask, int rounds, int record_words, int blocks = 0)
+      : who_(who), stream_(mask), blocks_(grid(who_, dev, mask, rounds, blocks)),
+        record_words_(record_words), out_(static_cast<size_t>(blocks_) * record_words) {}
 
   template <class Launch>
   void warm_up(Launch&& launch) {   // loads the code object
@@ -113,7 +114,7 @@ class CuSession {
   int blocks() const { return blocks_; }
 
  private:
-  static int grid(const std::string& who, int dev, const std::vector<uint32_t>& mask, int rounds) {
+  static int grid(const std::string& who, int dev, const std::vector<uint32_t>& mask, int rounds, int blocks) {
     if (rounds < 1 || rounds > 64) throw std::invalid_argument(who + ": rounds in 1..64");
     int cus = 0;
     if (mask.empty())
@@ -121,7 +122,7 @@ class CuSession {
     else
       for (uint32_t w : mask) cus += __builtin_popcount(w);
     if (cus <= 0 || cus > 4096) throw std::invalid_argument(who + ": the mask enables no CU");
-    return rounds * cus;
+    return blocks > 0 ? blocks : rounds * cus;
   }
 
   std::string who_;

@@ -348,8 +348,8 @@ class XcdSession : public CuSession {
  public:
   static constexpr const char* who = "xcd_check";
 
-  XcdSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t groups)
-      : CuSession(who, dev, mask, checked_rounds(rounds), sx::kRecordWords), groups_(groups), dir_(sx::kDirWords), init_(sx::kDirWords),
+  XcdSession(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t groups, int workgroups = 0)
+      : CuSession(who, dev, mask, checked_rounds(rounds), sx::kRecordWords, checked_blocks(workgroups)), groups_(groups), dir_(sx::kDirWords), init_(sx::kDirWords),
         slices_(static_cast<size_t>(checked_blocks(blocks())) * sx::kSliceBytes), tslices_(static_cast<size_t>(blocks()) * sx::kTicketBytes) {
     if (!groups || (groups & ~sx::kAllGroups)) throw std::invalid_argument(std::string(who) + ": no group, or an unknown one");
     const void* kernels[4] = {reinterpret_cast<const void*>(xcd_write_kernel), reinterpret_cast<const void*>(xcd_read_kernel),
@@ -398,7 +398,7 @@ class XcdSession : public CuSession {
     return rounds;
   }
   static int checked_blocks(int blocks) {
-    if (blocks > static_cast<int>(sx::kMaxBlocks)) throw std::invalid_argument(std::string(who) + ": more than 1024 workgroups");
+    if (blocks < 0 || blocks > static_cast<int>(sx::kMaxBlocks)) throw std::invalid_argument(std::string(who) + ": more than 1024 workgroups");
     return blocks;
   }
 
@@ -482,7 +482,7 @@ XcdInject xcd_parse_inject(const py::object& inject, int& atomic_word) {
 }
 
 py::dict xcd_check(int dev, const std::vector<uint32_t>& mask, int rounds, uint32_t seed, const std::vector<std::string>& groups,
-                   const py::object& inject, const py::object& corrupt) {
+                   const py::object& inject, const py::object& corrupt, int blocks) {
   const uint32_t bits = kXcdNames.bits(groups);
   int atomic_word = -1;
   const XcdInject inj = xcd_parse_inject(inject, atomic_word);
@@ -502,7 +502,7 @@ py::dict xcd_check(int dev, const std::vector<uint32_t>& mask, int rounds, uint3
   {
     py::gil_scoped_release nogil;
     HIP_OK(hipSetDevice(dev));
-    XcdSession session(dev, mask, rounds, bits);
+    XcdSession session(dev, mask, rounds, bits, blocks);
     session.set_corrupt(c);
     r = session.run(seed, inj);
     attr = session.attributes();
