@@ -7,8 +7,8 @@ one drives the probe's `cu_sweep` and `hbm_pattern_check` (native/hip/probe_swee
   is resident per CU and the dispatcher spreads them), run an exact bf16 MFMA chain on all 4
   waves and pattern-test the LDS. `fold_sweep` folds the per-workgroup records by CU identity
   `(xcc, (hw_id >> 8) & 0xFF)`. A CU that no workgroup reached is a coverage shortfall, not a
-  failure: `deep_selftest` re-launches with doubled rounds (3 launches at most), then reports
-  how many CUs it could not reach.
+  failure: `deep_selftest` re-launches with doubled rounds (`launch_until_covered`: 3 launches at
+  most), then reports how many CUs it could not reach.
 * `hbm_pattern_check` fills a buffer with words that are a function of their address and
   verifies it, then does the same with the complement. `pattern_word` / `pattern_at` are the
   host twin of that pattern, so a report (or a test) can state the expected value anywhere.
@@ -228,6 +228,21 @@ class Selection(make_dataclass("_PartFields", [(part.key, list, field(default_fa
         return cls(**{part.key: part.parse(specs.pop(part.key, None)) for part in PARTS}, **specs)
 
 
+def launch_until_covered(launch, fold, rounds: int = 4, max_launches: int = MAX_LAUNCHES) -> tuple[dict, int]:
+    """The policy for coverage: a CU that no workgroup reached is a shortfall, not a failure. `launch(rounds)` makes
+    one launch and returns the records it added; `fold(all records so far)` gives a report with "cus_uncovered".
+    Launches with rounds, 2 x rounds, 4 x rounds ... until nothing is uncovered or `max_launches` were made.
+    Returns (the last fold, launches made)."""
+    records, launches = [], 0
+    while True:
+        records.extend(launch(rounds))
+        launches += 1
+        report = fold(records)
+        if report["cus_uncovered"] == 0 or launches >= max_launches:
+            return report, launches
+        rounds *= 2
+
+
 def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_bytes: int = 0,
                   seed: int | None = None, rounds: int = 4, xcd=None, **select) -> DeepReport:
     """One deep check of HIP device `device` on the calling thread. `cu_mask_bits` restricts
@@ -263,27 +278,26 @@ def deep_selftest(P, device: int, cu_mask_bits: list[int] | None = None, hbm_byt
         cus = int(P.device_props(device)["cus"])
         mask = cumask.mask_words(cu_mask_bits, cus) if cu_mask_bits is not None else []
         expected = len(set(cu_mask_bits)) if cu_mask_bits is not None else cus
-        launches, r = 0, rounds
+        last = {}                                   # what the sweep's last launch returned
 
-        def launch(part: Part) -> dict:
+        def launch_part(part: Part, r: int) -> dict:
             result[part.key] = getattr(P, part.binding)(device, mask, r, seed, names[part.key])
             records[part.key].extend(result[part.key]["records"])
             return result[part.key]
 
-        while True:
+        def launch(r: int) -> list:
+            nonlocal last
             if in_sweep:
-                last = launch(in_sweep)
+                last = launch_part(in_sweep, r)
             else:
                 last = P.cu_sweep(device, mask, r, seed)
                 swept.extend(last["records"])
-            launches += 1
             for part in active:
                 if not part.in_sweep:
-                    launch(part)
-            sweep = fold_sweep([rec[:5] for rec in swept], expected)
-            if sweep["cus_uncovered"] == 0 or launches >= MAX_LAUNCHES:
-                break
-            r *= 2
+                    launch_part(part, r)
+            return last["records"]
+
+        sweep, launches = launch_until_covered(launch, lambda recs: fold_sweep([rec[:5] for rec in recs], expected), rounds)
         sweep.update(lds_bytes=int(last["lds_bytes"]), launches=launches, ms=float(last["ms"]))
         rep.sweep = sweep
         rep.cu_keys = sorted({(rec[0], cu_key(rec[1])) for rec in swept})

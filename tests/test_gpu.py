@@ -10,29 +10,9 @@ import json
 
 import pytest
 
+from gpu_harness import P, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md (merged back from the GPU box)."""
-    from pathlib import Path
-
-    p = Path("gpurun_out/gpu_facts.json")
-    p.parent.mkdir(exist_ok=True)
-    d = json.loads(p.read_text()) if p.exists() else {}
-    d[key] = value
-    p.write_text(json.dumps(d, indent=1))
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)  # fails loudly if the HIP extension is missing
 
 
 @pytest.fixture(scope="module")

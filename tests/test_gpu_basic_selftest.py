@@ -10,26 +10,9 @@ import numpy as np
 import pytest
 
 import bf16_tile_cases as K            # tests/ is on sys.path (no package)
+from gpu_harness import P, record
 
 pytestmark = pytest.mark.gpu
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 @pytest.fixture(scope="module", autouse=True)

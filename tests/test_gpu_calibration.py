@@ -7,20 +7,11 @@ import math
 
 import pytest
 
+from gpu_harness import P   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
 MIB = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 @pytest.fixture(scope="module")

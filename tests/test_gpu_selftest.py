@@ -5,29 +5,12 @@ import json
 
 import pytest
 
+from gpu_harness import SEED, P, a_cu_on_xcd3, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
 MIB = 1 << 20
-SEED = 0x1234ABCD
 BIG = 64 * MIB + 48          # full blocks plus a 3-element tail
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 @pytest.fixture(scope="module")
@@ -74,16 +57,10 @@ def test_masked_sweep_sees_the_cus_the_census_sees(P):
     assert rep["failed"] == [] and rep["uncovered"] == [] and rep["cus_seen"] == 64
 
 
-def _a_cu_on_xcd3(rep_records):
-    from nanogpu.probe.selftest_common import cu_key
-
-    return sorted({cu_key(h) for x, h, *_ in rep_records if x == 3})[5]
-
-
 def test_injected_mfma_fault_fails_exactly_that_cu(P, clean):
     from nanogpu.probe.selftest import fold_sweep
 
-    key = _a_cu_on_xcd3(clean[0]["records"])
+    key = a_cu_on_xcd3(clean[0]["records"])
     r = P.cu_sweep(0, [], 8, SEED, (3, key, "mfma"))
     rep = fold_sweep(r["records"], 256)
     assert rep["failed"] == [{"xcc": 3, "cu_key": key, "kinds": ["mfma"], "lds_bad_off": -1}], rep["failed"]
@@ -100,7 +77,7 @@ LDS_OFFSETS = {"last": lambda n: n - 1, "first": lambda n: 0, "255": lambda n: 2
 def test_injected_lds_fault_reports_the_offset(P, clean, where):
     from nanogpu.probe.selftest import fold_sweep
 
-    key = _a_cu_on_xcd3(clean[0]["records"])
+    key = a_cu_on_xcd3(clean[0]["records"])
     n = clean[0]["lds_bytes"] // 4              # 40960 when the workgroup holds all 160 KiB
     off = LDS_OFFSETS[where](n)
     r = P.cu_sweep(0, [], 8, SEED, (3, key, "lds", off))
@@ -116,7 +93,7 @@ def test_two_injected_cus_fold_to_two_cus_with_their_own_offsets(P, clean):
 
     n = clean[0]["lds_bytes"] // 4
     keys5 = sorted({cu_key(h) for x, h, *_ in clean[0]["records"] if x == 5})
-    first = (3, _a_cu_on_xcd3(clean[0]["records"]), n - 257)
+    first = (3, a_cu_on_xcd3(clean[0]["records"]), n - 257)
     second = (5, keys5[-1], 256)
     records = []
     for xcc, key, off in (first, second):

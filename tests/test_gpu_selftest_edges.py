@@ -9,25 +9,9 @@ import time
 
 import pytest
 
+from gpu_harness import P, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 def code_class(path, code):

@@ -14,40 +14,20 @@ from pathlib import Path
 
 import pytest
 
+from gpu_harness import SEED, P, a_cu_on_xcd3, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
 MIB = 1 << 20
 GIB = 1 << 30
-SEED = 0x1234ABCD
 UNIT = 8                     # mask bits of a unit on a whole MI355X: one CU on each XCD
 UNITS = 32
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 @pytest.fixture(scope="module")
 def cu_on_xcd3(P):
     """The CU the injections go to, picked as tests/test_gpu_selftest.py picks it."""
-    from nanogpu.probe.selftest_common import cu_key
-
-    r = P.cu_sweep(0, [], 8, SEED)
-    return sorted({cu_key(h) for x, h, *_ in r["records"] if x == 3})[5]
+    return a_cu_on_xcd3(P.cu_sweep(0, [], 8, SEED)["records"])
 
 
 class Injecting:

@@ -1,4 +1,5 @@
-"""The sweep's dynamic-LDS kernels on a real MI355X (`pytest -m gpu`). The occupancy query there
+"""The "part kernel" (nothing to do with `Part` or test_gpu_selftest_parts.py): the sweep's dynamic-LDS kernels on a
+real MI355X (`pytest -m gpu`). The occupancy query there
 always answers that a block may hold a CU's whole 160 KiB, so the instantiations with `n` dwords
 of dynamic LDS run only through the `lds_bytes` test hook of `cu_sweep` / `cu_sweep_paths`: clean
 at the smallest legal sizes, comparing (a corrupted expected word fails every record), with the
@@ -9,22 +10,12 @@ from collections import Counter
 
 import pytest
 
+from gpu_harness import SEED, P   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
-SEED = 0x1234ABCD
 STAGED = 36864            # 4 * kNumPaths * kTileWords: the nine expected tiles staged in LDS
 WORKGROUPS = 4 * 256      # rounds = 4, unmasked
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 def _paths():

@@ -9,48 +9,23 @@ import statistics
 
 import pytest
 
+from gpu_harness import SEED, P, a_cu_on_xcd3, record, sweep_all   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
-SEED = 0x1234ABCD
 
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
-
-
-def _sweep_all(P, rounds=4, inject=None):
-    """One unmasked path sweep with deep_selftest's own policy for coverage (a shortfall is not
-    a failure: doubled rounds, three launches at most)."""
+def _sweep_paths(P, rounds=4, inject=None):
+    """One unmasked sweep of every path: (its result, the sweep's fold of its records, the paths' fold)."""
     from nanogpu.probe.selftest import fold_sweep
-    from nanogpu.probe.selftest_paths import PATHS, fold_paths
+    from nanogpu.probe.selftest_paths import PART, PATHS
 
-    r = P.cu_sweep_paths(0, [], rounds, SEED, list(PATHS), inject)
-    records = list(r["records"])
-    for more in (rounds * 2, rounds * 4):
-        if fold_sweep([x[:5] for x in records], 256)["cus_uncovered"] == 0:
-            break
-        records += list(P.cu_sweep_paths(0, [], more, SEED, list(PATHS), inject)["records"])
-    r["records"] = records
-    return r, fold_sweep([x[:5] for x in records], 256), fold_paths(records, r["paths"], 256)
+    r, paths = sweep_all(P, PART, PATHS, rounds, inject)
+    return r, fold_sweep([x[:5] for x in r["records"]], 256), paths
 
 
 @pytest.fixture(scope="module")
 def clean(P):
-    return _sweep_all(P)
+    return _sweep_paths(P)
 
 
 # ----------------------------------------------------------------------------- one instruction
@@ -127,16 +102,10 @@ def test_path_sweep_reaches_every_cu_and_every_path_is_clean(P, clean):
     assert r["lds_bytes"] == P.device_props(0)["max_shared_per_cu_bytes"]
 
 
-def _a_cu_on_xcd3(records):
-    from nanogpu.probe.selftest_common import cu_key
-
-    return sorted({cu_key(x[1]) for x in records if x[0] == 3})[5]
-
-
 @pytest.mark.parametrize("path", ["f16", "fp8", "bf8", "i8", "mxfp8", "mxfp6", "mxfp4", "f32", "f64"])
 def test_injected_path_fault_fails_exactly_that_cu_and_path(P, clean, path):
-    key = _a_cu_on_xcd3(clean[0]["records"])
-    _r, rep, paths = _sweep_all(P, 8, (3, key, path))
+    key = a_cu_on_xcd3(clean[0]["records"])
+    _r, rep, paths = _sweep_paths(P, 8, (3, key, path))
     assert paths["failed"] == {path: [[3, key]]}, paths["failed"]
     assert paths["cus"] == [{"xcc": 3, "cu_key": key, "paths": [path], "waves": 1}], paths["cus"]
     assert rep["failed"] == []                       # the bf16 chain and the LDS are clean

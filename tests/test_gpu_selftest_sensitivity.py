@@ -8,28 +8,11 @@ import time
 
 import pytest
 
+from gpu_harness import SEED, P, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
-SEED = 0x1234ABCD
 TILES = ("bf16", "f16", "fp8", "bf8", "i8", "mxfp8", "mxfp6", "mxfp4", "f32", "f64")
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 def tile_words(name: str) -> int:

@@ -6,28 +6,11 @@ import time
 
 import pytest
 
+from gpu_harness import SEED, P, record   # tests/ is on sys.path (no package)
+
 pytestmark = pytest.mark.gpu
 
-SEED = 0x1234ABCD
 ALL_PAIRS = {(w, r) for w in range(8) for r in range(8)}
-
-
-def record(key: str, value) -> None:
-    """Measured facts for profiles/gpu_calibration.md, into the same file as test_gpu.py's."""
-    from test_gpu import record as record_fact   # tests/ is on sys.path (no package)
-
-    record_fact(key, value)
-
-
-@pytest.fixture(scope="module")
-def P():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    from nanogpu.native import probe
-
-    return probe(required=True)
 
 
 def _mask(bits):
@@ -165,6 +148,7 @@ def test_inject_atomic_fails_exactly_that_word(P, word):
 
 def test_corrupt_byte_is_reported_by_every_reader_with_writer_cu_and_word(P):
     from nanogpu.probe import selftest_xcd as X
+    from nanogpu.probe.selftest_common import cu_key
 
     word, byte, xor = 1234, 2, 0x40
     r, f = _run(P, _mask(UNIT), 1, corrupt=(3, 4 * word + byte, xor))
@@ -179,7 +163,7 @@ def test_corrupt_byte_is_reported_by_every_reader_with_writer_cu_and_word(P):
     if counts[wx] == 1:                                       # block 3 is its XCD's only slice: every reader reads it
         assert len(hit) == 8
     assert f["kinds"] == {"handoff": ["data"]} and f["failed"]["handoff"] == [list(p) for p in sorted({(wx, rd[0]) for rd in hit})]
-    assert f["first"]["handoff"]["writer"] == [wx, (whw >> 8) & 0xFF] and f["first"]["handoff"]["word"] == word
+    assert f["first"]["handoff"]["writer"] == [wx, cu_key(whw)] and f["first"]["handoff"]["word"] == word
     assert list(r["atomic_bad"]) == [] and f["failed"]["ticket"] == []
     for bad in ((8, 0, 1), (0, 16384, 1), (0, 0, 256)):
         with pytest.raises(ValueError):
