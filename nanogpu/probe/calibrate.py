@@ -265,21 +265,32 @@ def hbm_busy_calibration(P, device: int, busy_file, shares=(25, 100), seconds: f
     return cal if all(b > 0 for _, b in cal) else []
 
 
-def cu_share_mask(share_pct: float, cus: int = 256, xcds: int = 8) -> list[int]:
-    """Mask words of the node agent's grant for a `share_pct` % tenant (nanogpu.agent.cumask)."""
+def cu_share_mask(share_pct: float, cus: int = 256, xcds: int = 8, after_pct: float = 0) -> list[int]:
+    """Mask words of the node agent's grant for a `share_pct` % tenant (nanogpu.agent.cumask).
+    `after_pct` > 0: the grant the agent makes once another tenant holds that share of the device,
+    so that the two masks are disjoint."""
     from ..agent import cumask
 
     if share_pct >= 100:
         return cumask.mask_words(list(range(cus)), cus)
     d = cumask.DeviceCUs(cus, xcds)
+    if after_pct > 0:
+        d.grant("neighbour", int(round(after_pct)))
     return cumask.mask_words(d.grant("t", int(round(share_pct))), cus)
 
 
-def tenant_call(P, kind: str, mask: list[int], device: int = 0, seconds: float = 1.0):
+GEMM_MN = 8192   # M = N of the calibration's GEMM tenant: 4,096 workgroups, ten rounds of a 75 % mask at two a CU
+
+
+def tenant_call(P, kind: str, mask: list[int], device: int = 0, seconds: float = 1.0, k: int = 4096):
     """A callable that runs about `seconds` of one CU-masked tenant: "stream" (HBM copy, returns
-    GB/s) or "mfma" (bf16 burn, returns TFLOP/s). Each probe launch is bounded, so long runs
-    call it back to back."""
+    GB/s), "mfma" (bf16 burn, returns TFLOP/s) or "gemm" (bf16 GEMM of GEMM_MN x GEMM_MN x `k`, returns
+    TFLOP/s). Each probe launch is bounded, so long runs call it back to back."""
     n_cus = sum(bin(w).count("1") for w in mask)
+    if kind == "gemm":
+        trial = P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, 4)
+        iters = max(4, min(100000, int(4 * seconds * 1e3 / max(trial["ms"], 1e-3))))
+        return lambda: P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, iters)["tflops"]
     if kind == "stream":
         t = time.perf_counter()
         P.hbm_colocated(device, [mask], 1 << 30, 4)
@@ -336,3 +347,44 @@ def mem_busy_while(busy_file, runs: list, seconds: float = 8.0, ramp_s: float = 
                     "mean_nonzero": round(sum(nz) / len(nz), 1) if nz else 0.0,
                     "mean_1s": spaced(1.0), "mean_5s": spaced(5.0)})
     return res
+
+
+def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), busy_file=None,
+                      seconds: float = 0.25, nbytes: int = 1 << 30, busy_seconds: float = 3.0) -> list[dict]:
+    """What a matrix tenant with real memory traffic loses beside a streamer, and what it costs the streamer:
+    the probe's bf16 GEMM (GEMM_MN x GEMM_MN x k, memory-bound at k = 64 and bound by the matrix unit at 4096)
+    on the agent's `shares[1]` % mask and the HBM copy on its disjoint `shares[0]` % mask. Per k, each for about
+    `seconds`: the GEMM alone, the streamer alone, and both together twice, once with the copy sized to outlast
+    the GEMM three times over and once the other way round, so that each rate is measured entirely beside its
+    neighbour. One dict per k: the GEMM's TFLOP/s and the streamer's GB/s alone and beside, the fractions kept,
+    the GEMM's FLOP per compulsory byte and its compulsory GB/s alone (a lower bound on its HBM traffic), and,
+    with a `busy_file`, the mean mem_busy_percent of the lone GEMM over `busy_seconds` (mem_busy_while)."""
+    smask = cu_share_mask(shares[0])
+    gmask = cu_share_mask(shares[1], after_pct=shares[0])
+    mn = GEMM_MN
+
+    def count(ms_wanted: float, ms_each: float) -> int:
+        return max(2, min(100000, int(round(ms_wanted / max(ms_each, 1e-3)))))
+
+    copy_ms = 2e-6 * nbytes / max(P.hbm_colocated(device, [smask], nbytes, 4)[0], 1e-3)   # one copy: read + write
+    rows = []
+    for k in ks:
+        gemm_ms = P.gemm_throughput(device, gmask, mn, mn, k, 4)["ms"] / 4
+        g_iters, s_iters = count(seconds * 1e3, gemm_ms), min(1000, count(seconds * 1e3, copy_ms))
+        alone = P.gemm_throughput(device, gmask, mn, mn, k, g_iters)
+        stream_alone = P.hbm_colocated(device, [smask], nbytes, s_iters)[0]
+        gemm_beside = P.gemm_colocated(device, gmask, smask, mn, mn, k, g_iters, nbytes,
+                                       count(3 * g_iters * gemm_ms, copy_ms))[0]
+        stream_beside = P.gemm_colocated(device, gmask, smask, mn, mn, k, count(3 * s_iters * copy_ms, gemm_ms),
+                                         nbytes, s_iters)[1]
+        row = {"k": k, "gemm_tflops_alone": alone["tflops"], "gemm_tflops_beside": gemm_beside,
+               "gemm_kept": gemm_beside / alone["tflops"],
+               "stream_gbs_alone": stream_alone, "stream_gbs_beside": stream_beside,
+               "stream_kept": stream_beside / stream_alone,
+               "flop_per_byte": 2.0 * mn * mn * k / (2.0 * k * (mn + mn) + 4.0 * mn * mn),
+               "gemm_compulsory_gbs_alone": alone["gbs"]}
+        if busy_file is not None:
+            run = (f"gemm k={k}", tenant_call(P, "gemm", gmask, device, k=k))
+            row["mem_busy_percent"] = mem_busy_while(busy_file, [run], seconds=busy_seconds)[0]["mean_all"]
+        rows.append(row)
+    return rows

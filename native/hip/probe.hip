@@ -11,6 +11,8 @@
 //                   must scale with the CUs granted);
 //   * hbm_copy    — streaming HBM3E bandwidth (16 B/lane, grid >> 256 WGs);
 //                   these two rates, alone or co-located, are lists of Tenant behind one run_tenants;
+//   * gemm_bf16_kernel — a bf16 GEMM through HBM, L2 and LDS whose K sets its arithmetic intensity: the
+//                   tenant between the two, alone or beside a copy (gemm_throughput, gemm_colocated);
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
 //   * cu_sweep_kernel, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA
 //                   pipes and LDS (`cu_sweep`), and free HBM against an address-derived pattern.
@@ -44,6 +46,7 @@
 #include <utility>
 #include <vector>
 
+#include "nanogpu/gemm_host.h"
 #include "nanogpu/selftest_host.h"
 #include "nanogpu/selftest_mem_host.h"
 #include "nanogpu/selftest_paths_host.h"
@@ -73,6 +76,7 @@ namespace st = nanogpu::selftest;
 // instantiated in the order in which host code first names them, and that is the order of the
 // kernels in the code object.
 #include "probe_calibration.inc"    // hbm_copy, cu_census, mfma_burn, mfma_tile; DevBuf, Stream, Events; Tenant
+#include "probe_gemm.inc"           // gemm_bf16_kernel: the matrix tenant with memory traffic, Tenant's third kind
 #include "probe_selftest_core.inc"  // NameTable, CuSession, PartSession and the part bindings, Sensitivity
 #include "probe_sweep.inc"          // cu_sweep and cu_sweep_paths: the matrix unit and LDS
 #include "probe_valu.inc"           // cu_sweep_valu
@@ -165,6 +169,24 @@ PYBIND11_MODULE(_probe, m) {
   m.def("mfma_colocated", &mfma_colocated, py::arg("device"), py::arg("cu_masks"), py::arg("blocks"),
         py::arg("iters") = 2048, py::call_guard<py::gil_scoped_release>(),
         "Concurrent MFMA burns on CU-masked streams; per-stream TFLOP/s.");
+  m.def("gemm_bf16", &gemm_bf16, py::arg("a"), py::arg("b"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+        py::call_guard<py::gil_scoped_release>(),
+        "C[m][n] (floats, row-major) = bf16(a[m][k]) @ bf16(b[k][n]) by one launch of the GEMM tenant's kernel, fp32 "
+        "accumulation; a and b are lists of floats, rounded as gemm_tile rounds them. m and n are multiples of 128 and k "
+        "of 64, each at most 1024, else ValueError.");
+  m.def("gemm_throughput", &gemm_throughput, py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{},
+        py::arg("m") = 8192, py::arg("n") = 8192, py::arg("k") = 4096, py::arg("iters") = 10,
+        "bf16 GEMM on a CU-masked stream, `iters` launches: {ms, tflops, gbs, m, n, k, iters}. tflops is 2 m n k iters "
+        "over the time. gbs is the compulsory traffic over the same time, 2 k (m + n) + 4 m n bytes a launch (A and B "
+        "read once, C written once): a lower bound on the HBM traffic, not a counter. m and n are multiples of 128, k "
+        "of 64, m n / 128^2 and iters below 2^24, else ValueError; MemoryError when the operands do not fit.");
+  m.def("gemm_colocated", &gemm_colocated, py::arg("device"), py::arg("gemm_mask"), py::arg("hbm_mask"), py::arg("m") = 8192,
+        py::arg("n") = 8192, py::arg("k") = 4096, py::arg("gemm_iters") = 10, py::arg("bytes") = size_t(1) << 30,
+        py::arg("hbm_iters") = 10, py::call_guard<py::gil_scoped_release>(),
+        "[GEMM TFLOP/s, copy GB/s] for a bf16 GEMM tenant beside a streaming one, enqueued together on their own "
+        "CU-masked streams and each timed by its own events. The caller sizes which outlasts the other: the shorter "
+        "one is the one measured entirely beside its neighbour. Shapes as gemm_throughput's, bytes and hbm_iters as "
+        "mixed_colocated's.");
   m.def(
       "peer_bandwidth",
       [](int src, int dst, size_t bytes, int iters, double deadline_s) {

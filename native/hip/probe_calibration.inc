@@ -288,9 +288,15 @@ CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
   return res;
 }
 
+// probe_gemm.inc: one launch of the GEMM tenant's kernel, and of the fill of its operands, on a stream.
+void gemm_launch(hipStream_t s, const uint16_t* a, const uint16_t* b, float* c, int m, int n, int k);
+void gemm_fill(hipStream_t s, uint16_t* p, size_t count, uint32_t seed);
+double gemm_tflops(int m, int n, int k, int iters, double ms);
+
 // One tenant of a device in a rate probe: a stream under its CU mask (empty: every CU) with its own
-// events, and the work it repeats there: `iters` launches of an HBM copy of n float4, or one launch of an
-// MFMA burn of `blocks` blocks that loops `iters` times. The callers have checked the shapes.
+// events, and the work it repeats there: `iters` launches of an HBM copy of n float4, one launch of an
+// MFMA burn of `blocks` blocks that loops `iters` times, or `iters` launches of a bf16 GEMM of m x n x k on
+// operands it owns. The callers have checked the shapes.
 struct Tenant {
   Stream st;
   Events ev;
@@ -300,6 +306,9 @@ struct Tenant {
   DevBuf<float4> src, dst;
   int blocks = 0;   // a burn
   DevBuf<float> out;
+  int gemm_m = 0, gemm_n = 0, gemm_k = 0;   // a GEMM: gemm_m > 0
+  DevBuf<uint16_t> ga, gb;
+  DevBuf<float> gc;
 
   static Tenant copy(const std::vector<uint32_t>& mask, size_t n, unsigned grid, int iters) {
     Tenant t{Stream(mask), Events(), iters};
@@ -317,20 +326,38 @@ struct Tenant {
     t.out = DevBuf<float>(static_cast<size_t>(blocks) * 256);
     return t;
   }
+  // A and B are filled once, on the tenant's own stream like the copy's source. An allocation that does not
+  // fit is the caller's to shrink (MemoryError).
+  static Tenant gemm(const std::vector<uint32_t>& mask, int m, int n, int k, int iters) {
+    Tenant t{Stream(mask), Events(), iters};
+    t.gemm_m = m, t.gemm_n = n, t.gemm_k = k;
+    const size_t na = static_cast<size_t>(m) * k, nb = static_cast<size_t>(k) * n;
+    t.ga = DevBuf<uint16_t>(na, OomIsBadAlloc{});
+    t.gb = DevBuf<uint16_t>(nb, OomIsBadAlloc{});
+    t.gc = DevBuf<float>(static_cast<size_t>(m) * n, OomIsBadAlloc{});
+    gemm_fill(t.st.s, t.ga.p, na, 0xa11ce5edu);
+    gemm_fill(t.st.s, t.gb.p, nb, 0xb0b5eedu);
+    return t;
+  }
   void copy_once() const { hipLaunchKernelGGL(hbm_copy, dim3(grid), dim3(kCopyBlock), 0, st.s, src.p, dst.p, n); }
   void burn_once(int loops) const {
     hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, loops);
   }
-  void warm_up() const { n ? copy_once() : burn_once(8); }
+  void gemm_once() const { gemm_launch(st.s, ga.p, gb.p, gc.p, gemm_m, gemm_n, gemm_k); }
+  void warm_up() const { gemm_m ? gemm_once() : n ? copy_once() : burn_once(8); }
   void enqueue_timed() const {
     HIP_OK(hipEventRecord(ev.a, st.s));
-    if (n)
+    if (gemm_m)
+      for (int i = 0; i < iters; ++i) gemm_once();
+    else if (n)
       for (int i = 0; i < iters; ++i) copy_once();
     else
       burn_once(iters);
     HIP_OK(hipEventRecord(ev.b, st.s));
   }
-  double rate() { return n ? copy_gbs(n, iters, ev.ms()) : burn_tflops(blocks, iters, ev.ms()); }
+  double rate() {
+    return gemm_m ? gemm_tflops(gemm_m, gemm_n, gemm_k, iters, ev.ms()) : n ? copy_gbs(n, iters, ev.ms()) : burn_tflops(blocks, iters, ev.ms());
+  }
 };
 
 // The one procedure behind the rate probes. Every tenant warms up and the device drains; then the timed

@@ -8,7 +8,8 @@ about half of the device's bandwidth (profiles/gpu_calibration.md), so a fixed f
 threshold would miss small streamers; this measures the activity curve the share-aware
 threshold is built from (nanogpu.types.HBM_STREAMING_CURVE). Sampling: nanogpu.probe.calibrate
 .mem_busy_while (a child process reads the counter every 10 ms; every sample of the window
-counts, as in avg_over_time).
+counts, as in avg_over_time). `--gemm-shares` adds the kind gemm, the probe's bf16 GEMM tenant
+(`--gemm-k`: memory-bound at 64, bound by the matrix unit at 4096).
 
     python tools/hbm_share_calibration.py --out gpurun_out/hbm_share.json
 """
@@ -29,6 +30,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="gpurun_out/hbm_share_calibration.json")
     ap.add_argument("--stream-shares", default="12.5,25,50,100")
     ap.add_argument("--mfma-shares", default="25,75,100")
+    ap.add_argument("--gemm-shares", default="", help="shares for the kind gemm, the bf16 GEMM tenant (none by default)")
+    ap.add_argument("--gemm-k", type=int, default=4096, help="the GEMM's K: 64 is memory-bound, 4096 compute-bound")
     a = ap.parse_args(argv)
 
     import torch  # the HIP runtime first (nanogpu.native.probe loads after torch)
@@ -42,10 +45,11 @@ def main(argv=None) -> int:
     if f is None:
         raise SystemExit("mem_busy_percent not exposed")
     runs = []
-    for kind, shares in (("stream", a.stream_shares), ("mfma", a.mfma_shares)):
+    for kind, shares in (("stream", a.stream_shares), ("mfma", a.mfma_shares), ("gemm", a.gemm_shares)):
         for s in (float(x) for x in shares.split(",") if x):
             mask = C.cu_share_mask(s)
-            runs.append((f"{kind} {s:g}% ({sum(bin(w).count('1') for w in mask)} CUs)", C.tenant_call(P, kind, mask)))
+            label = f"{kind} k={a.gemm_k}" if kind == "gemm" else kind
+            runs.append((f"{label} {s:g}% ({sum(bin(w).count('1') for w in mask)} CUs)", C.tenant_call(P, kind, mask, k=a.gemm_k)))
     res = {"file": str(f), "runs": C.mem_busy_while(f, runs, a.seconds)}
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(res, indent=1))
