@@ -280,13 +280,24 @@ def cu_share_mask(share_pct: float, cus: int = 256, xcds: int = 8, after_pct: fl
 
 
 GEMM_MN = 8192   # M = N of the calibration's GEMM tenant: 4,096 workgroups, ten rounds of a 75 % mask at two a CU
+# (heads, sq, skv) of the calibration's attention tenants. Prefill: 2,048 workgroups of the wide kernel. Decode: 32
+# queries a head against a cache of 4,096, one workgroup of the split kernel a head, so 2,048 workgroups again: four
+# rounds of the 512 a whole device holds at two a CU, 4 GiB of K and V a launch.
+ATTN_WIDE = (64, 4096, 4096)
+ATTN_SPLIT = (2048, 32, 4096)
 
 
-def tenant_call(P, kind: str, mask: list[int], device: int = 0, seconds: float = 1.0, k: int = 4096):
+def tenant_call(P, kind: str, mask: list[int], device: int = 0, seconds: float = 1.0, k: int = 4096,
+                attn: tuple = ATTN_WIDE):
     """A callable that runs about `seconds` of one CU-masked tenant: "stream" (HBM copy, returns
-    GB/s), "mfma" (bf16 burn, returns TFLOP/s) or "gemm" (bf16 GEMM of GEMM_MN x GEMM_MN x `k`, returns
-    TFLOP/s). Each probe launch is bounded, so long runs call it back to back."""
+    GB/s), "mfma" (bf16 burn, returns TFLOP/s), "gemm" (bf16 GEMM of GEMM_MN x GEMM_MN x `k`, returns
+    TFLOP/s) or "attn" (bf16 attention of `attn` = (heads, sq, skv), returns TFLOP/s). Each probe launch is
+    bounded, so long runs call it back to back."""
     n_cus = sum(bin(w).count("1") for w in mask)
+    if kind == "attn":
+        trial = P.attn_throughput(device, mask, *attn, 4)
+        iters = max(4, min(100000, int(4 * seconds * 1e3 / max(trial["ms"], 1e-3))))
+        return lambda: P.attn_throughput(device, mask, *attn, iters)["tflops"]
     if kind == "gemm":
         trial = P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, 4)
         iters = max(4, min(100000, int(4 * seconds * 1e3 / max(trial["ms"], 1e-3))))
@@ -349,6 +360,28 @@ def mem_busy_while(busy_file, runs: list, seconds: float = 8.0, ramp_s: float = 
     return res
 
 
+def _beside_streamer(P, device, smask, throughput, colocated, copy_ms: float, seconds: float, nbytes: int):
+    """One row's measurements of a matrix tenant and the HBM copy on `smask`, each for about `seconds`: the tenant
+    alone (`throughput(iters)`, a probe's *_throughput dict), the streamer alone, and both together twice
+    (`colocated(tenant iters, copy iters)`, a probe's *_colocated pair), once with the copy sized to outlast the
+    tenant three times over and once the other way round, so that each rate is measured entirely beside its
+    neighbour. Returns (the tenant's dict alone, its TFLOP/s beside, the streamer's GB/s alone, beside)."""
+    def count(ms_wanted: float, ms_each: float) -> int:
+        return max(2, min(100000, int(round(ms_wanted / max(ms_each, 1e-3)))))
+
+    tenant_ms = throughput(4)["ms"] / 4
+    t_iters, s_iters = count(seconds * 1e3, tenant_ms), min(1000, count(seconds * 1e3, copy_ms))
+    alone = throughput(t_iters)
+    stream_alone = P.hbm_colocated(device, [smask], nbytes, s_iters)[0]
+    tenant_beside = colocated(t_iters, count(3 * t_iters * tenant_ms, copy_ms))[0]
+    stream_beside = colocated(count(3 * s_iters * copy_ms, tenant_ms), s_iters)[1]
+    return alone, tenant_beside, stream_alone, stream_beside
+
+
+def _copy_ms(P, device, smask, nbytes: int) -> float:
+    return 2e-6 * nbytes / max(P.hbm_colocated(device, [smask], nbytes, 4)[0], 1e-3)   # one copy: read + write
+
+
 def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), busy_file=None,
                       seconds: float = 0.25, nbytes: int = 1 << 30, busy_seconds: float = 3.0) -> list[dict]:
     """What a matrix tenant with real memory traffic loses beside a streamer, and what it costs the streamer:
@@ -362,21 +395,13 @@ def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), b
     smask = cu_share_mask(shares[0])
     gmask = cu_share_mask(shares[1], after_pct=shares[0])
     mn = GEMM_MN
-
-    def count(ms_wanted: float, ms_each: float) -> int:
-        return max(2, min(100000, int(round(ms_wanted / max(ms_each, 1e-3)))))
-
-    copy_ms = 2e-6 * nbytes / max(P.hbm_colocated(device, [smask], nbytes, 4)[0], 1e-3)   # one copy: read + write
+    copy_ms = _copy_ms(P, device, smask, nbytes)
     rows = []
     for k in ks:
-        gemm_ms = P.gemm_throughput(device, gmask, mn, mn, k, 4)["ms"] / 4
-        g_iters, s_iters = count(seconds * 1e3, gemm_ms), min(1000, count(seconds * 1e3, copy_ms))
-        alone = P.gemm_throughput(device, gmask, mn, mn, k, g_iters)
-        stream_alone = P.hbm_colocated(device, [smask], nbytes, s_iters)[0]
-        gemm_beside = P.gemm_colocated(device, gmask, smask, mn, mn, k, g_iters, nbytes,
-                                       count(3 * g_iters * gemm_ms, copy_ms))[0]
-        stream_beside = P.gemm_colocated(device, gmask, smask, mn, mn, k, count(3 * s_iters * copy_ms, gemm_ms),
-                                         nbytes, s_iters)[1]
+        alone, gemm_beside, stream_alone, stream_beside = _beside_streamer(
+            P, device, smask, lambda iters: P.gemm_throughput(device, gmask, mn, mn, k, iters),
+            lambda g_iters, s_iters: P.gemm_colocated(device, gmask, smask, mn, mn, k, g_iters, nbytes, s_iters),
+            copy_ms, seconds, nbytes)
         row = {"k": k, "gemm_tflops_alone": alone["tflops"], "gemm_tflops_beside": gemm_beside,
                "gemm_kept": gemm_beside / alone["tflops"],
                "stream_gbs_alone": stream_alone, "stream_gbs_beside": stream_beside,
@@ -385,6 +410,36 @@ def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), b
                "gemm_compulsory_gbs_alone": alone["gbs"]}
         if busy_file is not None:
             run = (f"gemm k={k}", tenant_call(P, "gemm", gmask, device, k=k))
+            row["mem_busy_percent"] = mem_busy_while(busy_file, [run], seconds=busy_seconds)[0]["mean_all"]
+        rows.append(row)
+    return rows
+
+
+def attn_interference(P, device: int = 0, shares=(25, 75), shapes=(ATTN_WIDE, ATTN_SPLIT), busy_file=None,
+                      seconds: float = 0.25, nbytes: int = 1 << 30, busy_seconds: float = 3.0) -> list[dict]:
+    """gemm_interference for the tenant a transformer server is: the probe's bf16 attention of each (heads, sq, skv)
+    of `shapes`, by default one prefill shape (the wide kernel) and one decode shape (the split kernel, memory-bound
+    at any size), on the agent's `shares[1]` % mask beside the HBM copy on its disjoint `shares[0]` % mask, by the
+    same procedure. One dict per shape, with gemm_interference's columns under attn_* names, the shape and the
+    kernel that served it."""
+    smask = cu_share_mask(shares[0])
+    amask = cu_share_mask(shares[1], after_pct=shares[0])
+    copy_ms = _copy_ms(P, device, smask, nbytes)
+    rows = []
+    for heads, sq, skv in shapes:
+        alone, attn_beside, stream_alone, stream_beside = _beside_streamer(
+            P, device, smask, lambda iters: P.attn_throughput(device, amask, heads, sq, skv, iters),
+            lambda a_iters, s_iters: P.attn_colocated(device, amask, smask, heads, sq, skv, a_iters, nbytes, s_iters),
+            copy_ms, seconds, nbytes)
+        row = {"heads": heads, "sq": sq, "skv": skv, "kernel": alone["kernel"],
+               "attn_tflops_alone": alone["tflops"], "attn_tflops_beside": attn_beside,
+               "attn_kept": attn_beside / alone["tflops"],
+               "stream_gbs_alone": stream_alone, "stream_gbs_beside": stream_beside,
+               "stream_kept": stream_beside / stream_alone,
+               "flop_per_byte": 4.0 * 128 * sq * skv / (256.0 * (sq + 2 * skv) + 512.0 * sq),
+               "attn_compulsory_gbs_alone": alone["gbs"]}
+        if busy_file is not None:
+            run = (f"attn {alone['kernel']}", tenant_call(P, "attn", amask, device, attn=(heads, sq, skv)))
             row["mem_busy_percent"] = mem_busy_while(busy_file, [run], seconds=busy_seconds)[0]["mean_all"]
         rows.append(row)
     return rows

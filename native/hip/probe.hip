@@ -13,6 +13,8 @@
 //                   these two rates, alone or co-located, are lists of Tenant behind one run_tenants;
 //   * gemm_bf16_kernel — a bf16 GEMM through HBM, L2 and LDS whose K sets its arithmetic intensity: the
 //                   tenant between the two, alone or beside a copy (gemm_throughput, gemm_colocated);
+//   * attn_bf16_kernel — fused bf16 attention forward by the online softmax, wide for prefill and split-KV for
+//                   decode: the tenant a transformer server is (attn_throughput, attn_colocated);
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
 //   * cu_sweep_kernel, hbm_fill / hbm_verify — the agent's deep self-test: every CU's MFMA
 //                   pipes and LDS (`cu_sweep`), and free HBM against an address-derived pattern.
@@ -46,6 +48,7 @@
 #include <utility>
 #include <vector>
 
+#include "nanogpu/attn_host.h"
 #include "nanogpu/gemm_host.h"
 #include "nanogpu/selftest_host.h"
 #include "nanogpu/selftest_mem_host.h"
@@ -77,6 +80,7 @@ namespace st = nanogpu::selftest;
 // kernels in the code object.
 #include "probe_calibration.inc"    // hbm_copy, cu_census, mfma_burn, mfma_tile; DevBuf, Stream, Events; Tenant
 #include "probe_gemm.inc"           // gemm_bf16_kernel: the matrix tenant with memory traffic, Tenant's third kind
+#include "probe_attn.inc"           // attn_bf16_kernel: fused attention, wide and split-KV, Tenant's fourth kind
 #include "probe_selftest_core.inc"  // NameTable, CuSession, PartSession and the part bindings, Sensitivity
 #include "probe_sweep.inc"          // cu_sweep and cu_sweep_paths: the matrix unit and LDS
 #include "probe_valu.inc"           // cu_sweep_valu
@@ -187,6 +191,27 @@ PYBIND11_MODULE(_probe, m) {
         "CU-masked streams and each timed by its own events. The caller sizes which outlasts the other: the shorter "
         "one is the one measured entirely beside its neighbour. Shapes as gemm_throughput's, bytes and hbm_iters as "
         "mixed_colocated's.");
+  m.def("attn_bf16", &attn_bf16, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("heads"), py::arg("sq"), py::arg("skv"),
+        py::arg("device") = 0, py::call_guard<py::gil_scoped_release>(),
+        "O[heads][sq][128] (floats, row-major) = softmax(q k^T / sqrt(128)) v per head, non-causal, by one launch of the "
+        "attention tenant's kernel: q is [heads][sq][128], k and v [heads][skv][128], lists of floats rounded to bf16 as "
+        "gemm_tile rounds them; fp32 accumulation, the weights rounded to bf16 before they meet v. sq is a multiple of "
+        "128 and skv of 64 (the wide kernel), or sq 32, 64 or 96 and skv a multiple of 128 (the split kernel); heads at "
+        "most 8, sq 512 and skv 1024, else ValueError.");
+  m.def("attn_throughput", &attn_throughput, py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{},
+        py::arg("heads") = 64, py::arg("sq") = 4096, py::arg("skv") = 4096, py::arg("iters") = 10,
+        "bf16 attention forward on a CU-masked stream, `iters` launches: {ms, tflops, gbs, heads, sq, skv, iters, kernel}. "
+        "tflops is 4 heads sq skv 128 iters over the time. gbs is the compulsory traffic over the same time, 256 heads "
+        "(sq + 2 skv) + 512 heads sq bytes a launch (Q, K and V read once, O written once): a lower bound on the HBM "
+        "traffic, not a counter. kernel is 'wide' (sq a multiple of 128, skv of 64) or 'split' (sq 32, 64 or 96, skv a "
+        "multiple of 128); the workgroups and iters stay below 2^24, else ValueError; MemoryError when the operands do "
+        "not fit.");
+  m.def("attn_colocated", &attn_colocated, py::arg("device"), py::arg("attn_mask"), py::arg("hbm_mask"), py::arg("heads") = 64,
+        py::arg("sq") = 4096, py::arg("skv") = 4096, py::arg("attn_iters") = 10, py::arg("bytes") = size_t(1) << 30,
+        py::arg("hbm_iters") = 10, py::call_guard<py::gil_scoped_release>(),
+        "[attention TFLOP/s, copy GB/s] for a bf16 attention tenant beside a streaming one, as gemm_colocated: enqueued "
+        "together on their own CU-masked streams, each timed by its own events, the caller sizing which outlasts the "
+        "other. Shapes as attn_throughput's, bytes and hbm_iters as mixed_colocated's.");
   m.def(
       "peer_bandwidth",
       [](int src, int dst, size_t bytes, int iters, double deadline_s) {

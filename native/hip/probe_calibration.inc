@@ -292,26 +292,35 @@ CopyCheck copy_check(int dev, size_t n_floats, size_t guard_bytes) {
 void gemm_launch(hipStream_t s, const uint16_t* a, const uint16_t* b, float* c, int m, int n, int k);
 void gemm_fill(hipStream_t s, uint16_t* p, size_t count, uint32_t seed);
 double gemm_tflops(int m, int n, int k, int iters, double ms);
+// probe_attn.inc: the same of the attention tenant's kernel.
+void attn_launch(hipStream_t s, const uint16_t* q, const uint16_t* k, const uint16_t* v, float* o, int heads, int sq, int skv);
+double attn_tflops(int heads, int sq, int skv, int iters, double ms);
 
 // One tenant of a device in a rate probe: a stream under its CU mask (empty: every CU) with its own
 // events, and the work it repeats there: `iters` launches of an HBM copy of n float4, one launch of an
-// MFMA burn of `blocks` blocks that loops `iters` times, or `iters` launches of a bf16 GEMM of m x n x k on
-// operands it owns. The callers have checked the shapes.
+// MFMA burn of `blocks` blocks that loops `iters` times, `iters` launches of a bf16 GEMM of m x n x k on
+// operands it owns, or `iters` launches of a bf16 attention of heads x sq x skv on its own Q, K and V. The
+// callers have checked the shapes.
 struct Tenant {
+  enum class Kind { kBurn, kCopy, kGemm, kAttn };
   Stream st;
   Events ev;
   int iters;
-  size_t n = 0;   // a copy: n > 0
+  Kind kind = Kind::kBurn;
+  size_t n = 0;   // a copy
   unsigned grid = 0;
   DevBuf<float4> src, dst;
   int blocks = 0;   // a burn
   DevBuf<float> out;
-  int gemm_m = 0, gemm_n = 0, gemm_k = 0;   // a GEMM: gemm_m > 0
-  DevBuf<uint16_t> ga, gb;
-  DevBuf<float> gc;
+  int gemm_m = 0, gemm_n = 0, gemm_k = 0;   // a GEMM
+  DevBuf<uint16_t> ga, gb;                  // A and B; an attention's Q and K
+  DevBuf<float> gc;                         // C; an attention's O
+  int attn_heads = 0, attn_sq = 0, attn_skv = 0;   // an attention
+  DevBuf<uint16_t> gv;
 
   static Tenant copy(const std::vector<uint32_t>& mask, size_t n, unsigned grid, int iters) {
     Tenant t{Stream(mask), Events(), iters};
+    t.kind = Kind::kCopy;
     t.n = n;
     t.grid = grid;
     t.src = DevBuf<float4>(n);
@@ -330,6 +339,7 @@ struct Tenant {
   // fit is the caller's to shrink (MemoryError).
   static Tenant gemm(const std::vector<uint32_t>& mask, int m, int n, int k, int iters) {
     Tenant t{Stream(mask), Events(), iters};
+    t.kind = Kind::kGemm;
     t.gemm_m = m, t.gemm_n = n, t.gemm_k = k;
     const size_t na = static_cast<size_t>(m) * k, nb = static_cast<size_t>(k) * n;
     t.ga = DevBuf<uint16_t>(na, OomIsBadAlloc{});
@@ -344,19 +354,36 @@ struct Tenant {
     hipLaunchKernelGGL(mfma_burn<false>, dim3(blocks), dim3(256), 0, st.s, out.p, loops);
   }
   void gemm_once() const { gemm_launch(st.s, ga.p, gb.p, gc.p, gemm_m, gemm_n, gemm_k); }
-  void warm_up() const { gemm_m ? gemm_once() : n ? copy_once() : burn_once(8); }
+  void attn_once() const { attn_launch(st.s, ga.p, gb.p, gv.p, gc.p, attn_heads, attn_sq, attn_skv); }
+  // Q, K and V are filled once, on the tenant's own stream (probe_attn.inc).
+  static Tenant attn(const std::vector<uint32_t>& mask, int heads, int sq, int skv, int iters);
+  // One launch of the tenant's work; the burn loops `loops` times inside its one launch.
+  void once(int loops) const {
+    switch (kind) {
+      case Kind::kBurn: return burn_once(loops);
+      case Kind::kCopy: return copy_once();
+      case Kind::kGemm: return gemm_once();
+      case Kind::kAttn: return attn_once();
+    }
+  }
+  void warm_up() const { once(8); }
   void enqueue_timed() const {
     HIP_OK(hipEventRecord(ev.a, st.s));
-    if (gemm_m)
-      for (int i = 0; i < iters; ++i) gemm_once();
-    else if (n)
-      for (int i = 0; i < iters; ++i) copy_once();
+    if (kind == Kind::kBurn)
+      once(iters);
     else
-      burn_once(iters);
+      for (int i = 0; i < iters; ++i) once(0);
     HIP_OK(hipEventRecord(ev.b, st.s));
   }
   double rate() {
-    return gemm_m ? gemm_tflops(gemm_m, gemm_n, gemm_k, iters, ev.ms()) : n ? copy_gbs(n, iters, ev.ms()) : burn_tflops(blocks, iters, ev.ms());
+    const double ms = ev.ms();
+    switch (kind) {
+      case Kind::kBurn: return burn_tflops(blocks, iters, ms);
+      case Kind::kCopy: return copy_gbs(n, iters, ms);
+      case Kind::kGemm: return gemm_tflops(gemm_m, gemm_n, gemm_k, iters, ms);
+      case Kind::kAttn: return attn_tflops(attn_heads, attn_sq, attn_skv, iters, ms);
+    }
+    return 0.0;
   }
 };
 
