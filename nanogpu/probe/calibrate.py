@@ -291,17 +291,18 @@ def tenant_call(P, kind: str, mask: list[int], device: int = 0, seconds: float =
                 attn: tuple = ATTN_WIDE):
     """A callable that runs about `seconds` of one CU-masked tenant: "stream" (HBM copy, returns
     GB/s), "mfma" (bf16 burn, returns TFLOP/s), "gemm" (bf16 GEMM of GEMM_MN x GEMM_MN x `k`, returns
-    TFLOP/s) or "attn" (bf16 attention of `attn` = (heads, sq, skv), returns TFLOP/s). Each probe launch is
-    bounded, so long runs call it back to back."""
+    TFLOP/s), "gemm_fp8" (the same GEMM on e4m3 operands, `k` a multiple of 128) or "attn" (bf16 attention of
+    `attn` = (heads, sq, skv), returns TFLOP/s). Each probe launch is bounded, so long runs call it back to back."""
     n_cus = sum(bin(w).count("1") for w in mask)
     if kind == "attn":
         trial = P.attn_throughput(device, mask, *attn, 4)
         iters = max(4, min(100000, int(4 * seconds * 1e3 / max(trial["ms"], 1e-3))))
         return lambda: P.attn_throughput(device, mask, *attn, iters)["tflops"]
-    if kind == "gemm":
-        trial = P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, 4)
+    if kind in ("gemm", "gemm_fp8"):
+        dtype = ("fp8",) if kind == "gemm_fp8" else ()   # a probe from before the option takes no dtype
+        trial = P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, 4, *dtype)
         iters = max(4, min(100000, int(4 * seconds * 1e3 / max(trial["ms"], 1e-3))))
-        return lambda: P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, iters)["tflops"]
+        return lambda: P.gemm_throughput(device, mask, GEMM_MN, GEMM_MN, k, iters, *dtype)["tflops"]
     if kind == "stream":
         t = time.perf_counter()
         P.hbm_colocated(device, [mask], 1 << 30, 4)
@@ -382,8 +383,9 @@ def _copy_ms(P, device, smask, nbytes: int) -> float:
     return 2e-6 * nbytes / max(P.hbm_colocated(device, [smask], nbytes, 4)[0], 1e-3)   # one copy: read + write
 
 
-def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), busy_file=None,
-                      seconds: float = 0.25, nbytes: int = 1 << 30, busy_seconds: float = 3.0) -> list[dict]:
+def gemm_interference(P, device: int = 0, shares=(25, 75), ks=None, busy_file=None,
+                      seconds: float = 0.25, nbytes: int = 1 << 30, busy_seconds: float = 3.0,
+                      dtype: str = "bf16") -> list[dict]:
     """What a matrix tenant with real memory traffic loses beside a streamer, and what it costs the streamer:
     the probe's bf16 GEMM (GEMM_MN x GEMM_MN x k, memory-bound at k = 64 and bound by the matrix unit at 4096)
     on the agent's `shares[1]` % mask and the HBM copy on its disjoint `shares[0]` % mask. Per k, each for about
@@ -391,25 +393,32 @@ def gemm_interference(P, device: int = 0, shares=(25, 75), ks=(64, 512, 4096), b
     the GEMM three times over and once the other way round, so that each rate is measured entirely beside its
     neighbour. One dict per k: the GEMM's TFLOP/s and the streamer's GB/s alone and beside, the fractions kept,
     the GEMM's FLOP per compulsory byte and its compulsory GB/s alone (a lower bound on its HBM traffic), and,
-    with a `busy_file`, the mean mem_busy_percent of the lone GEMM over `busy_seconds` (mem_busy_while)."""
+    with a `busy_file`, the mean mem_busy_percent of the lone GEMM over `busy_seconds` (mem_busy_while).
+    `ks` defaults to (64, 512, 4096). `dtype` "fp8" measures the probe's e4m3 GEMM instead (every k a multiple of
+    128, by default (128, 512, 4096)): the probe is then passed the trailing "fp8", the rows carry "dtype", and a
+    byte an operand element counts in flop_per_byte."""
     smask = cu_share_mask(shares[0])
     gmask = cu_share_mask(shares[1], after_pct=shares[0])
     mn = GEMM_MN
     copy_ms = _copy_ms(P, device, smask, nbytes)
+    extra, operand_bytes = ((), 2.0) if dtype == "bf16" else ((dtype,), 1.0)
+    ks = ks if ks is not None else (128, 512, 4096) if extra else (64, 512, 4096)
     rows = []
     for k in ks:
         alone, gemm_beside, stream_alone, stream_beside = _beside_streamer(
-            P, device, smask, lambda iters: P.gemm_throughput(device, gmask, mn, mn, k, iters),
-            lambda g_iters, s_iters: P.gemm_colocated(device, gmask, smask, mn, mn, k, g_iters, nbytes, s_iters),
+            P, device, smask, lambda iters: P.gemm_throughput(device, gmask, mn, mn, k, iters, *extra),
+            lambda g_iters, s_iters: P.gemm_colocated(device, gmask, smask, mn, mn, k, g_iters, nbytes, s_iters, *extra),
             copy_ms, seconds, nbytes)
         row = {"k": k, "gemm_tflops_alone": alone["tflops"], "gemm_tflops_beside": gemm_beside,
                "gemm_kept": gemm_beside / alone["tflops"],
                "stream_gbs_alone": stream_alone, "stream_gbs_beside": stream_beside,
                "stream_kept": stream_beside / stream_alone,
-               "flop_per_byte": 2.0 * mn * mn * k / (2.0 * k * (mn + mn) + 4.0 * mn * mn),
+               "flop_per_byte": 2.0 * mn * mn * k / (operand_bytes * k * (mn + mn) + 4.0 * mn * mn),
                "gemm_compulsory_gbs_alone": alone["gbs"]}
+        if extra:
+            row["dtype"] = dtype
         if busy_file is not None:
-            run = (f"gemm k={k}", tenant_call(P, "gemm", gmask, device, k=k))
+            run = (f"gemm {dtype} k={k}" if extra else f"gemm k={k}", tenant_call(P, "gemm_fp8" if extra else "gemm", gmask, device, k=k))
             row["mem_busy_percent"] = mem_busy_while(busy_file, [run], seconds=busy_seconds)[0]["mean_all"]
         rows.append(row)
     return rows

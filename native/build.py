@@ -151,6 +151,7 @@ SELFTEST_HOST_TARGETS = {   # target -> (program's stem, its main, the headers i
             ["selftest_host.h", "selftest_paths_host.h", "selftest_xcd_host.h"]),
     "gemm": ("nanogpu-gemm-host", "gemm_host_main.cpp", ["gemm_host.h"]),
     "attn": ("nanogpu-attn-host", "attn_host_main.cpp", ["gemm_host.h", "attn_host.h"]),
+    "gemmfp8": ("nanogpu-gemm-fp8-host", "gemm_fp8_host_main.cpp", ["gemm_host.h", "gemm_fp8_host.h"]),
 }
 # --selftest-host's values: "plain" and "asan" for target "host", "<target>-plain" and "<target>-asan" for the others
 SELFTEST_HOST_CHOICES = [kind if target == "host" else f"{target}-{kind}"
@@ -206,7 +207,7 @@ def main() -> None:
     ap.add_argument("--stress", choices=list(SANITIZERS), help="build the native stress driver")
     ap.add_argument("--selftest-host", choices=SELFTEST_HOST_CHOICES,
                     help="build the stand-alone check of the deep self-test's host arithmetic "
-                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups', xcd-*: the XCD check's, gemm-*: the GEMM tenant's tile map, shapes and indices, attn-*: the attention tenant's)")
+                         "(paths-*: the matrix paths' header, valu-*: the vector-ALU groups', scalar-*: the scalar groups', mem-*: the memory groups', xcd-*: the XCD check's, gemm-*: the GEMM tenant's tile map, shapes and indices, attn-*: the attention tenant's, gemmfp8-*: the FP8 GEMM tenant's shapes, swizzle and indices)")
     a = ap.parse_args()
     if a.stress:
         print(build_stress(a.stress, force=a.force))

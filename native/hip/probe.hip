@@ -13,6 +13,8 @@
 //                   these two rates, alone or co-located, are lists of Tenant behind one run_tenants;
 //   * gemm_bf16_kernel — a bf16 GEMM through HBM, L2 and LDS whose K sets its arithmetic intensity: the
 //                   tenant between the two, alone or beside a copy (gemm_throughput, gemm_colocated);
+//   * gemm_fp8_kernel — the same GEMM on e4m3 operands, B stored [N][K], on the 32x32x64 block-scaled MFMA with unit
+//                   scales: the tenant an FP8 inference server is (gemm_fp8; dtype "fp8" of the two GEMM probes);
 //   * attn_bf16_kernel — fused bf16 attention forward by the online softmax, wide for prefill and split-KV for
 //                   decode: the tenant a transformer server is (attn_throughput, attn_colocated);
 //   * peer_bandwidth — per-pair xGMI rate: copy kernel pulling over peer access, and SDMA
@@ -49,6 +51,7 @@
 #include <vector>
 
 #include "nanogpu/attn_host.h"
+#include "nanogpu/gemm_fp8_host.h"
 #include "nanogpu/gemm_host.h"
 #include "nanogpu/selftest_host.h"
 #include "nanogpu/selftest_mem_host.h"
@@ -81,6 +84,7 @@ namespace st = nanogpu::selftest;
 #include "probe_calibration.inc"    // hbm_copy, cu_census, mfma_burn, mfma_tile; DevBuf, Stream, Events; Tenant
 #include "probe_gemm.inc"           // gemm_bf16_kernel: the matrix tenant with memory traffic, Tenant's third kind
 #include "probe_attn.inc"           // attn_bf16_kernel: fused attention, wide and split-KV, Tenant's fourth kind
+#include "probe_gemm_fp8.inc"       // gemm_fp8_kernel: the e4m3 GEMM on the 32x32x64 scaled MFMA, Tenant's fifth kind
 #include "probe_selftest_core.inc"  // NameTable, CuSession, PartSession and the part bindings, Sensitivity
 #include "probe_sweep.inc"          // cu_sweep and cu_sweep_paths: the matrix unit and LDS
 #include "probe_valu.inc"           // cu_sweep_valu
@@ -178,16 +182,23 @@ PYBIND11_MODULE(_probe, m) {
         "C[m][n] (floats, row-major) = bf16(a[m][k]) @ bf16(b[k][n]) by one launch of the GEMM tenant's kernel, fp32 "
         "accumulation; a and b are lists of floats, rounded as gemm_tile rounds them. m and n are multiples of 128 and k "
         "of 64, each at most 1024, else ValueError.");
+  m.def("gemm_fp8", &gemm_fp8, py::arg("a_codes"), py::arg("b_codes"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+        "C[m][n] (floats, row-major) = A . B^T by one launch of the FP8 GEMM tenant's kernel, fp32 accumulation: a_codes is "
+        "A[m][k] and b_codes B[n][k], e4m3 (OCP) codes, each a one-dimensional contiguous uint8 buffer or a list of ints. "
+        "The codes reach the device as they are: nothing is rounded. m, n and k are multiples of 128, each at most 1024, "
+        "else ValueError.");
   m.def("gemm_throughput", &gemm_throughput, py::arg("device") = 0, py::arg("cu_mask") = std::vector<uint32_t>{},
-        py::arg("m") = 8192, py::arg("n") = 8192, py::arg("k") = 4096, py::arg("iters") = 10,
-        "bf16 GEMM on a CU-masked stream, `iters` launches: {ms, tflops, gbs, m, n, k, iters}. tflops is 2 m n k iters "
+        py::arg("m") = 8192, py::arg("n") = 8192, py::arg("k") = 4096, py::arg("iters") = 10, py::arg("dtype") = "bf16",
+        "GEMM on a CU-masked stream, `iters` launches: {ms, tflops, gbs, m, n, k, iters, dtype}. tflops is 2 m n k iters "
         "over the time. gbs is the compulsory traffic over the same time, 2 k (m + n) + 4 m n bytes a launch (A and B "
         "read once, C written once): a lower bound on the HBM traffic, not a counter. m and n are multiples of 128, k "
-        "of 64, m n / 128^2 and iters below 2^24, else ValueError; MemoryError when the operands do not fit.");
+        "of 64, m n / 128^2 and iters below 2^24, else ValueError; MemoryError when the operands do not fit. dtype 'fp8' "
+        "runs the e4m3 kernel (B stored [n][k]): k is then a multiple of 128 and a launch's traffic k (m + n) + 4 m n; "
+        "any dtype but 'bf16' and 'fp8' is a ValueError.");
   m.def("gemm_colocated", &gemm_colocated, py::arg("device"), py::arg("gemm_mask"), py::arg("hbm_mask"), py::arg("m") = 8192,
         py::arg("n") = 8192, py::arg("k") = 4096, py::arg("gemm_iters") = 10, py::arg("bytes") = size_t(1) << 30,
-        py::arg("hbm_iters") = 10, py::call_guard<py::gil_scoped_release>(),
-        "[GEMM TFLOP/s, copy GB/s] for a bf16 GEMM tenant beside a streaming one, enqueued together on their own "
+        py::arg("hbm_iters") = 10, py::arg("dtype") = "bf16", py::call_guard<py::gil_scoped_release>(),
+        "[GEMM TFLOP/s, copy GB/s] for a GEMM tenant (dtype 'bf16' or 'fp8', as gemm_throughput's) beside a streaming one, enqueued together on their own "
         "CU-masked streams and each timed by its own events. The caller sizes which outlasts the other: the shorter "
         "one is the one measured entirely beside its neighbour. Shapes as gemm_throughput's, bytes and hbm_iters as "
         "mixed_colocated's.");

@@ -295,14 +295,17 @@ double gemm_tflops(int m, int n, int k, int iters, double ms);
 // probe_attn.inc: the same of the attention tenant's kernel.
 void attn_launch(hipStream_t s, const uint16_t* q, const uint16_t* k, const uint16_t* v, float* o, int heads, int sq, int skv);
 double attn_tflops(int heads, int sq, int skv, int iters, double ms);
+// probe_gemm_fp8.inc: the same of the FP8 GEMM tenant's kernel, and its shape check.
+void gemm_fp8_launch(hipStream_t s, const uint8_t* a, const uint8_t* b, float* c, int m, int n, int k);
+void check_gemm_fp8(const char* who, long long m, long long n, long long k, long long iters);
 
 // One tenant of a device in a rate probe: a stream under its CU mask (empty: every CU) with its own
 // events, and the work it repeats there: `iters` launches of an HBM copy of n float4, one launch of an
 // MFMA burn of `blocks` blocks that loops `iters` times, `iters` launches of a bf16 GEMM of m x n x k on
-// operands it owns, or `iters` launches of a bf16 attention of heads x sq x skv on its own Q, K and V. The
-// callers have checked the shapes.
+// operands it owns, `iters` launches of a bf16 attention of heads x sq x skv on its own Q, K and V, or `iters`
+// launches of an e4m3 GEMM of m x n x k on its own A [m][k] and B [n][k]. The callers have checked the shapes.
 struct Tenant {
-  enum class Kind { kBurn, kCopy, kGemm, kAttn };
+  enum class Kind { kBurn, kCopy, kGemm, kAttn, kGemmFp8 };
   Stream st;
   Events ev;
   int iters;
@@ -317,6 +320,7 @@ struct Tenant {
   DevBuf<float> gc;                         // C; an attention's O
   int attn_heads = 0, attn_sq = 0, attn_skv = 0;   // an attention
   DevBuf<uint16_t> gv;
+  DevBuf<uint8_t> fa, fb;   // an FP8 GEMM's A and B; its shape and C are the GEMM's
 
   static Tenant copy(const std::vector<uint32_t>& mask, size_t n, unsigned grid, int iters) {
     Tenant t{Stream(mask), Events(), iters};
@@ -357,6 +361,9 @@ struct Tenant {
   void attn_once() const { attn_launch(st.s, ga.p, gb.p, gv.p, gc.p, attn_heads, attn_sq, attn_skv); }
   // Q, K and V are filled once, on the tenant's own stream (probe_attn.inc).
   static Tenant attn(const std::vector<uint32_t>& mask, int heads, int sq, int skv, int iters);
+  // A and B are filled once with e4m3 codes, on the tenant's own stream (probe_gemm_fp8.inc).
+  static Tenant gemm_fp8(const std::vector<uint32_t>& mask, int m, int n, int k, int iters);
+  void gemm_fp8_once() const { gemm_fp8_launch(st.s, fa.p, fb.p, gc.p, gemm_m, gemm_n, gemm_k); }
   // One launch of the tenant's work; the burn loops `loops` times inside its one launch.
   void once(int loops) const {
     switch (kind) {
@@ -364,6 +371,7 @@ struct Tenant {
       case Kind::kCopy: return copy_once();
       case Kind::kGemm: return gemm_once();
       case Kind::kAttn: return attn_once();
+      case Kind::kGemmFp8: return gemm_fp8_once();
     }
   }
   void warm_up() const { once(8); }
@@ -380,7 +388,8 @@ struct Tenant {
     switch (kind) {
       case Kind::kBurn: return burn_tflops(blocks, iters, ms);
       case Kind::kCopy: return copy_gbs(n, iters, ms);
-      case Kind::kGemm: return gemm_tflops(gemm_m, gemm_n, gemm_k, iters, ms);
+      case Kind::kGemm:
+      case Kind::kGemmFp8: return gemm_tflops(gemm_m, gemm_n, gemm_k, iters, ms);
       case Kind::kAttn: return attn_tflops(attn_heads, attn_sq, attn_skv, iters, ms);
     }
     return 0.0;

@@ -140,25 +140,38 @@ std::vector<float> gemm_bf16(const std::vector<float>& a, const std::vector<floa
   return c;
 }
 
-py::dict gemm_throughput(int dev, const std::vector<uint32_t>& mask, int m, int n, int k, int iters) {
+// The operand type of a GEMM tenant, "bf16" or "fp8" (gemm_fp8_kernel, probe_gemm_fp8.inc); anything else is refused.
+bool gemm_is_fp8(const char* who, const std::string& dtype) {
+  if (dtype != "bf16" && dtype != "fp8") throw std::invalid_argument(std::string(who) + ": dtype is 'bf16' or 'fp8'");
+  return dtype == "fp8";
+}
+
+// The checked tenant of either type: every refusal comes before any allocation or launch.
+Tenant gemm_tenant(const char* who, int dev, const std::vector<uint32_t>& mask, int m, int n, int k, int iters, bool fp8) {
+  (fp8 ? check_gemm_fp8 : check_gemm)(who, m, n, k, iters);
+  HIP_OK(hipSetDevice(dev));
+  return fp8 ? Tenant::gemm_fp8(mask, m, n, k, iters) : Tenant::gemm(mask, m, n, k, iters);
+}
+
+py::dict gemm_throughput(int dev, const std::vector<uint32_t>& mask, int m, int n, int k, int iters, const std::string& dtype) {
   double ms = 0.0, tflops = 0.0;
+  const bool fp8 = gemm_is_fp8("gemm_throughput", dtype);
   {
     py::gil_scoped_release nogil;
-    check_gemm("gemm_throughput", m, n, k, iters);
-    HIP_OK(hipSetDevice(dev));
     std::vector<Tenant> tenants;
-    tenants.push_back(Tenant::gemm(mask, m, n, k, iters));
+    tenants.push_back(gemm_tenant("gemm_throughput", dev, mask, m, n, k, iters, fp8));
     tflops = run_tenants(tenants)[0];
     ms = tenants[0].ev.ms();
   }
   py::dict d;
   d["ms"] = ms;
   d["tflops"] = tflops;
-  d["gbs"] = gm::compulsory_bytes(m, n, k) * iters / (ms * 1e-3) / 1e9;
+  d["gbs"] = (fp8 ? nanogpu::gemm_fp8::compulsory_bytes(m, n, k) : gm::compulsory_bytes(m, n, k)) * iters / (ms * 1e-3) / 1e9;
   d["m"] = m;
   d["n"] = n;
   d["k"] = k;
   d["iters"] = iters;
+  d["dtype"] = dtype;
   return d;
 }
 
@@ -166,14 +179,13 @@ py::dict gemm_throughput(int dev, const std::vector<uint32_t>& mask, int m, int 
 // together on their own CU-masked streams, each timed by its own events. The caller sizes which outlasts the
 // other: the shorter one is the one measured entirely beside its neighbour. Returns {GEMM TFLOP/s, copy GB/s}.
 std::vector<double> gemm_colocated(int dev, const std::vector<uint32_t>& gemm_mask, const std::vector<uint32_t>& hbm_mask,
-                                   int m, int n, int k, int gemm_iters, size_t bytes, int hbm_iters) {
-  check_gemm("gemm_colocated", m, n, k, gemm_iters);
+                                   int m, int n, int k, int gemm_iters, size_t bytes, int hbm_iters, const std::string& dtype) {
+  const bool fp8 = gemm_is_fp8("gemm_colocated", dtype);
   const size_t count = bytes / sizeof(float4);
   if (count == 0 || hbm_iters <= 0) throw std::invalid_argument("gemm_colocated: bytes and hbm_iters must be positive");
   const unsigned grid = copy_grid(count);
-  HIP_OK(hipSetDevice(dev));
   std::vector<Tenant> tenants;
-  tenants.push_back(Tenant::gemm(gemm_mask, m, n, k, gemm_iters));
+  tenants.push_back(gemm_tenant("gemm_colocated", dev, gemm_mask, m, n, k, gemm_iters, fp8));
   tenants.push_back(Tenant::copy(hbm_mask, count, grid, hbm_iters));
   return run_tenants(tenants);
 }

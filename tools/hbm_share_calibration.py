@@ -9,7 +9,8 @@ threshold would miss small streamers; this measures the activity curve the share
 threshold is built from (nanogpu.types.HBM_STREAMING_CURVE). Sampling: nanogpu.probe.calibrate
 .mem_busy_while (a child process reads the counter every 10 ms; every sample of the window
 counts, as in avg_over_time). `--gemm-shares` adds the kind gemm, the probe's bf16 GEMM tenant
-(`--gemm-k`: memory-bound at 64, bound by the matrix unit at 4096). `--attn-shares` adds the kind attn,
+(`--gemm-k`: memory-bound at 64, bound by the matrix unit at 4096). `--gemm-fp8-shares` adds the kind gemm_fp8,
+the same GEMM on e4m3 operands (`--gemm-k` a multiple of 128). `--attn-shares` adds the kind attn,
 the bf16 attention tenant (`--attn-shape heads,sq,skv`: sq below 128 is the memory-bound decode form).
 
     python tools/hbm_share_calibration.py --out gpurun_out/hbm_share.json
@@ -33,6 +34,7 @@ def main(argv=None) -> int:
     ap.add_argument("--mfma-shares", default="25,75,100")
     ap.add_argument("--gemm-shares", default="", help="shares for the kind gemm, the bf16 GEMM tenant (none by default)")
     ap.add_argument("--gemm-k", type=int, default=4096, help="the GEMM's K: 64 is memory-bound, 4096 compute-bound")
+    ap.add_argument("--gemm-fp8-shares", default="", help="shares for the kind gemm_fp8, the e4m3 GEMM tenant (none by default)")
     ap.add_argument("--attn-shares", default="", help="shares for the kind attn, the bf16 attention tenant (none by default)")
     ap.add_argument("--attn-shape", default="64,4096,4096", help="the attention's heads,sq,skv: sq below 128 is the decode form")
     a = ap.parse_args(argv)
@@ -50,10 +52,10 @@ def main(argv=None) -> int:
         raise SystemExit("mem_busy_percent not exposed")
     runs = []
     for kind, shares in (("stream", a.stream_shares), ("mfma", a.mfma_shares), ("gemm", a.gemm_shares),
-                         ("attn", a.attn_shares)):
+                         ("gemm_fp8", a.gemm_fp8_shares), ("attn", a.attn_shares)):
         for s in (float(x) for x in shares.split(",") if x):
             mask = C.cu_share_mask(s)
-            label = f"{kind} k={a.gemm_k}" if kind == "gemm" else f"{kind} {a.attn_shape}" if kind == "attn" else kind
+            label = f"{kind} k={a.gemm_k}" if kind in ("gemm", "gemm_fp8") else f"{kind} {a.attn_shape}" if kind == "attn" else kind
             runs.append((f"{label} {s:g}% ({sum(bin(w).count('1') for w in mask)} CUs)", C.tenant_call(P, kind, mask, k=a.gemm_k, attn=attn)))
     res = {"file": str(f), "runs": C.mem_busy_while(f, runs, a.seconds)}
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
